@@ -17,7 +17,7 @@ test-gpu:
 	python3 -m pytest tests/ -q -m gpu
 
 bench:
-	python3 bench.py --gpus 1 --steps 500 --warmup 50
+	python3 bench.py --gpus 1 --steps 500 --warmup 50 --full
 
 images: dp-image labeller-image ubi-dp-image ubi-labeller-image
 

@@ -10,8 +10,13 @@ against the live device plugin (real kfd sysfs on a GPU box; synthetic
 Contract (driver):
   python bench.py --gpus N --steps K --warmup W
 prints ONE JSON line from rank 0; multi-rank runs come via torchrun with
-one rank per GPU (rank 0 drives the node-local plugin, every rank verifies
-its own GPU is present and participates in the timing barriers).
+one rank per GPU (rank 0 drives the node-local plugin, every rank
+participates in the timing barriers).
+
+Such a plain run only sets up, warms up, times the K steps and reports.
+--full adds everything else: the per-rank checked matmul, the compiled
+C-client latency, and the opt-in --curve / --hbm-probe measurements.
+--dump-outputs DIR stores what the last timed step returned, as .npy.
 """
 
 from __future__ import annotations
@@ -30,6 +35,41 @@ def _dist_env():
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     return world, rank, local_rank
+
+
+def _pin_to_own_l3():
+    """Restrict this process to the allowed CPUs that share an L3 cache
+    with the CPU it is running on; returns the CPU list (None: not pinned).
+
+    A step is a chain of thread wake-ups between the client, its grpc
+    poller and the plugin's server thread.  Left to the scheduler on a
+    many-die host those threads share a die in one run and not in the
+    next, and identical runs differ by a factor of two (figures in
+    docs/benchmarks.md).  The group is the one the scheduler chose for
+    this process, so concurrent runs do not all pile onto the same CPUs.
+    Must run before any thread is created: only threads started afterwards
+    inherit the mask.
+    """
+    if not hasattr(os, "sched_setaffinity"):
+        return None
+    try:
+        allowed = os.sched_getaffinity(0)
+        with open("/proc/self/stat") as f:
+            # field 39 (processor); the command name may hold spaces
+            here = int(f.read().rsplit(")", 1)[1].split()[36])
+        with open(f"/sys/devices/system/cpu/cpu{here}"
+                  "/cache/index3/shared_cpu_list") as f:
+            shared = set()
+            for part in f.read().strip().split(","):
+                lo, _, hi = part.partition("-")
+                shared.update(range(int(lo), int(hi or lo) + 1))
+        cpus = sorted(shared & allowed)
+        if not cpus:
+            return None
+        os.sched_setaffinity(0, cpus)
+        return cpus
+    except (OSError, ValueError, IndexError):
+        return None
 
 
 def main() -> int:
@@ -51,11 +91,29 @@ def main() -> int:
     ap.add_argument("--fake-partitions", type=int, default=1,
                     help="with --sysfs fake: CPX-style partitions per GPU "
                          "(8 -> 64 logical devices, BASELINE config 4)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: "
+                         "per-rank checked GPU matmul, C-client latencies, "
+                         "and --curve / --hbm-probe when given")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the responses of the "
+                         "last step to DIR/<name>.npy")
+    ap.add_argument("--cpu-pin", choices=["l3", "none"], default="l3",
+                    help="l3: keep the run's threads on the CPUs sharing "
+                         "one L3 cache (repeatable timings); none: leave "
+                         "placement to the scheduler")
     args = ap.parse_args()
+    if (args.curve or args.hbm_probe) and not args.full:
+        ap.error("--curve and --hbm-probe are extra measurements: add --full")
+
+    world, rank, local_rank = _dist_env()
+    # only rank 0 runs the steps; before torch, which starts threads
+    pinned_cpus = None
+    if rank == 0 and args.cpu_pin == "l3":
+        pinned_cpus = _pin_to_own_l3()
 
     import torch
 
-    world, rank, local_rank = _dist_env()
     dist = None
     if world > 1:
         import torch.distributed as dist_mod
@@ -69,9 +127,14 @@ def main() -> int:
     # launched on a partially-visible box)
     cuda = torch.cuda.is_available() and local_rank < present_gpus
 
-    # ---- advertised-vs-present: every rank touches its own GPU ----
     if cuda:
         torch.cuda.set_device(local_rank)
+        # bring the HIP runtime up here, before the harness starts and
+        # warms up: left to the first timing barrier it would start its
+        # threads between the warmup and the timed steps and disturb them
+        torch.cuda.synchronize()
+    # ---- advertised-vs-present: every rank touches its own GPU ----
+    if cuda and args.full:
         x = torch.ones(1024, 1024, device=f"cuda:{local_rank}")
         y = (x @ x).sum()
         assert float(y) == 1024.0 * 1024 * 1024, "GPU sanity matmul failed"
@@ -127,6 +190,7 @@ def main() -> int:
     if rank == 0 and curve_ns:
         curve_out = _run_curve(harness, curve_ns, args.steps, args.warmup)
 
+    calls_before = len(harness.alloc_lat_us) if rank == 0 else 0
     barrier_sync()
     t0 = time.perf_counter()
     if rank == 0:
@@ -149,7 +213,12 @@ def main() -> int:
             statistics.median(harness.pref_lat_us) if harness.pref_lat_us else None
         )
         advertised = harness.advertised
-        native_client_p50 = harness.native_client_p50_us()
+        timed_allocates = len(harness.alloc_lat_us) - calls_before
+        if args.dump_outputs:
+            harness.dump_outputs(args.dump_outputs)
+        native_client_p50 = (
+            harness.native_client_p50_us() if args.full else None
+        )
         harness.stop()
 
         value = args.gpus * args.steps / elapsed  # device-grants/s, whole job
@@ -182,6 +251,9 @@ def main() -> int:
                 "sysfs": harness.sysfs_kind,
                 "advertised_gpus": advertised,
                 "present_gpus": present_gpus,
+                "pinned_cpus": len(pinned_cpus) if pinned_cpus else 0,
+                # Allocate round trips recorded inside the timed window
+                "timed_allocates": timed_allocates,
                 "allocate_p50_us": round(alloc_p50_us, 1),
                 "allocate_p99_us": round(alloc_p99_us, 1),
                 "native_client_allocate_p50_us": native_client_p50,
@@ -248,6 +320,8 @@ class _Harness:
         self.advertised = 0
         self.sysfs_kind = "unknown"
         self.last_chosen = []
+        self.last_pref_resp = None
+        self.last_alloc_resp = None
         self._tmp = None
         self._mgr = None
         self._kubelet = None
@@ -259,7 +333,11 @@ class _Harness:
         from k8s_device_plugin_amd.testing.stub_kubelet import StubKubelet
         from k8s_device_plugin_amd.topology import SysPaths, simple_health_check
 
-        self._tmp = tempfile.TemporaryDirectory(prefix="amdxdp-bench-")
+        from k8s_device_plugin_amd.testing.sockdir import short_tmp_root
+
+        self._tmp = tempfile.TemporaryDirectory(
+            prefix="amdxdp-bench-", dir=short_tmp_root()
+        )
         root = self._tmp.name
 
         live = SysPaths("/")
@@ -337,6 +415,7 @@ class _Harness:
             resp = self._stub.GetPreferredAllocation(req, timeout=10)
             t1 = time.perf_counter()
             self.pref_lat_us.append((t1 - t0) * 1e6)
+            self.last_pref_resp = resp
             chosen = list(resp.container_responses[0].deviceIDs)
         else:
             chosen = self.device_ids[:n]
@@ -349,10 +428,69 @@ class _Harness:
         aresp = self._stub.Allocate(areq, timeout=10)
         t1 = time.perf_counter()
         self.alloc_lat_us.append((t1 - t0) * 1e6)
+        self.last_alloc_resp = aresp
         specs = aresp.container_responses[0].devices
         assert len(specs) == 1 + 2 * n, (
             f"expected /dev/kfd + 2 nodes per device, got {len(specs)}"
         )
+
+    def dump_outputs(self, out_dir: str) -> None:
+        """Write what the last step() received as <out_dir>/<name>.npy.
+
+        The step's results are protobuf messages.  Their fields are stored
+        decoded -- granted_device_indices (positions of the granted devices
+        in the sorted advertised ID list), allocate_device_nodes (one row
+        per DeviceSpec: kind 0 /dev/kfd, 1 card, 2 renderD, 3 other; the
+        node number; 1 if host and container path agree) and
+        allocate_counts (devices, mounts, envs, annotations, CDI devices)
+        -- and, for an exact comparison, as their deterministic wire
+        encoding, one byte per float32 element (a few hundred bytes).  The
+        requests are a pure function of the advertised list and of --gpus,
+        so two builds run with the same arguments on the same node can be
+        compared array for array.
+        """
+        import re
+
+        import numpy as np
+
+        if self.last_alloc_resp is None:
+            raise RuntimeError("--dump-outputs needs at least one step")
+
+        def wire(msg):
+            raw = msg.SerializeToString(deterministic=True)
+            return np.frombuffer(raw, dtype=np.uint8).astype(np.float32)
+
+        def save(name, arr):
+            np.save(os.path.join(out_dir, name + ".npy"), arr)
+
+        os.makedirs(out_dir, exist_ok=True)
+        index = {d: i for i, d in enumerate(self.device_ids)}
+        save("granted_device_indices",
+             np.array([index[d] for d in self.last_chosen], dtype=np.float64))
+
+        cr = self.last_alloc_resp.container_responses[0]
+        nodes = []
+        for spec in cr.devices:
+            m = re.fullmatch(r"/dev/(?:kfd|dri/(card|renderD)(\d+))",
+                             spec.host_path)
+            if m is None:
+                kind, num = 3, -1
+            elif m.group(1) is None:
+                kind, num = 0, -1
+            else:
+                kind, num = (1 if m.group(1) == "card" else 2), int(m.group(2))
+            nodes.append(
+                [kind, num, float(spec.host_path == spec.container_path)]
+            )
+        save("allocate_device_nodes",
+             np.array(nodes, dtype=np.float64).reshape(-1, 3))
+        save("allocate_counts", np.array(
+            [len(cr.devices), len(cr.mounts), len(cr.envs),
+             len(cr.annotations), len(cr.cdi_devices)], dtype=np.float64))
+
+        save("allocate_response_bytes", wire(self.last_alloc_resp))
+        if self.last_pref_resp is not None:
+            save("preferred_response_bytes", wire(self.last_pref_resp))
 
     def hive_count(self, device_ids) -> int:
         """Distinct xGMI hives spanned by a device-ID set (1 = packed)."""

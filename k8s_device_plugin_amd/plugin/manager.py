@@ -162,8 +162,7 @@ class PluginManager:
         except OSError:
             return None
 
-    def _watch_loop(self) -> None:
-        last = self._socket_ident()
+    def _watch_loop(self, last: Optional[tuple]) -> None:
         while not self._stop.wait(self.watch_interval):
             cur = self._socket_ident()
             if cur is not None and cur != last:
@@ -186,10 +185,16 @@ class PluginManager:
 
     def run(self, resources: List[str]) -> None:
         os.makedirs(self.device_plugin_path, exist_ok=True)
+        # sample the socket before the first registration attempt: a kubelet
+        # that comes up while registration is failing, or right after run()
+        # returns, must look (re)created to the watch, not like the state it
+        # started from (registering twice is harmless)
+        seen = self._socket_ident()
         for res in resources:
             self.start_resource(res)
         self._watch_thread = threading.Thread(
-            target=self._watch_loop, daemon=True, name="kubelet-sock-watch"
+            target=self._watch_loop, args=(seen,),
+            daemon=True, name="kubelet-sock-watch",
         )
         self._watch_thread.start()
 

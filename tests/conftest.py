@@ -1,5 +1,9 @@
+import itertools
 import os
+import pathlib
+import shutil
 import sys
+import tempfile
 
 import pytest
 
@@ -23,6 +27,51 @@ def pytest_configure(config):
         nb.build_healthprobe()
     except Exception:
         pass  # no hipcc on this machine; gpu-marked tests need it anyway
+
+
+class _ShortTmpFactory:
+    """Stand-in for pytest's TempPathFactory (mktemp/getbasetemp only) that
+    hands out <short root>/dpt-XXXXXXXX/<basename>N directories.
+
+    Most tests here bind unix sockets under their temporary directory, and
+    pytest's own base (<tmp>/pytest-of-<user>/pytest-N/<test name>N/) can
+    use up most of sun_path's 107 bytes before the test adds
+    "device-plugins/kubelet.sock": the suite passed or failed with the
+    length of the user name and of $TMPDIR."""
+
+    def __init__(self):
+        from k8s_device_plugin_amd.testing.sockdir import short_tmp_root
+
+        self._base = pathlib.Path(
+            tempfile.mkdtemp(prefix="dpt-", dir=short_tmp_root())
+        )
+        self._count = itertools.count()
+
+    def getbasetemp(self) -> pathlib.Path:
+        return self._base
+
+    def mktemp(self, basename: str, numbered: bool = True) -> pathlib.Path:
+        name = f"{basename}{next(self._count)}" if numbered else basename
+        path = self._base / name
+        path.mkdir()
+        return path
+
+    def cleanup(self) -> None:
+        shutil.rmtree(self._base, ignore_errors=True)
+
+
+@pytest.fixture(scope="session")
+def tmp_path_factory():
+    factory = _ShortTmpFactory()
+    yield factory
+    factory.cleanup()
+
+
+@pytest.fixture
+def tmp_path(tmp_path_factory):
+    path = tmp_path_factory.mktemp("t")
+    yield path
+    shutil.rmtree(path, ignore_errors=True)
 
 
 @pytest.fixture

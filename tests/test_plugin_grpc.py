@@ -265,6 +265,39 @@ def test_register_fails_gracefully_without_kubelet(tmp_path, fake_mi355x_8):
         mgr.stop()
 
 
+def test_kubelet_appearing_while_registration_fails_is_registered_with(
+    tmp_path, fake_mi355x_8, monkeypatch
+):
+    """A kubelet whose socket appears during the failed first registration
+    (so before the watch thread runs) must still count as (re)created."""
+    dp_dir = str(tmp_path / "dp")
+    mgr = PluginManager(
+        lambda r: AMDGPUPlugin(resource=r, paths=fake_mi355x_8.paths),
+        device_plugin_path=dp_dir, watch_interval=0.05,
+    )
+    kubelet = StubKubelet(dp_dir)
+    real_register = mgr.register
+    calls = []
+
+    def register(inst, retries=5):
+        calls.append(inst.resource)
+        if len(calls) == 1:
+            # the first attempt "fails", and the kubelet comes up meanwhile
+            kubelet.start()
+            return False
+        return real_register(inst, retries)
+
+    monkeypatch.setattr(mgr, "register", register)
+    try:
+        mgr.run(["gpu"])
+        reg = kubelet.wait_for_registration(timeout=10)
+        assert reg.resource_name == "amd.com/gpu"
+        assert len(calls) >= 2
+    finally:
+        mgr.stop()
+        kubelet.stop()
+
+
 def test_native_unavailable_falls_back(tmp_path, fake_mi355x_8, monkeypatch):
     """If the fast server can't load, the manager serves via python grpc."""
     import k8s_device_plugin_amd.plugin.native_server as ns
