@@ -3,12 +3,16 @@ IMAGE_DP ?= rocm/k8s-device-plugin-mi355x
 IMAGE_NL ?= rocm/k8s-node-labeller-mi355x
 TAG ?= $(shell git describe --always --dirty 2>/dev/null || echo dev)
 
-.PHONY: all native test test-gpu bench images dp-image labeller-image ubi-dp-image ubi-labeller-image helm clean
+.PHONY: all native sweeps test test-gpu bench images dp-image labeller-image ubi-dp-image ubi-labeller-image helm clean
 
 all: native
 
 native:
 	PYTORCH_ROCM_ARCH=gfx950 python3 -m k8s_device_plugin_amd.native.build
+
+# stand-alone mfma_bench / hbm_bench: the probe's kernels against their variants
+sweeps:
+	PYTORCH_ROCM_ARCH=gfx950 python3 -m k8s_device_plugin_amd.native.build --sweeps
 
 test:
 	python3 -m pytest tests/ -q -m "not gpu"
@@ -37,7 +41,7 @@ helm:
 	helm lint deploy/helm/amd-gpu
 
 clean:
-	rm -f k8s_device_plugin_amd/native/*.so
+	rm -f k8s_device_plugin_amd/native/*.so k8s_device_plugin_amd/native/mfma_bench k8s_device_plugin_amd/native/hbm_bench
 	find . -name __pycache__ -type d -exec rm -rf {} +
 
 # ASAN + TSAN over the native-server matrix; logs in profiles/sanitizers/

@@ -25,10 +25,12 @@ def _python_includes() -> list:
     ]
 
 
-def _needs_build(src: str, out: str) -> bool:
+def _needs_build(out: str, *inputs: str) -> bool:
+    """True when out is missing or any input is newer than it."""
     if not os.path.exists(out):
         return True
-    return os.path.getmtime(src) > os.path.getmtime(out)
+    built = os.path.getmtime(out)
+    return any(os.path.getmtime(src) > built for src in inputs)
 
 
 def _run(cmd: list) -> None:
@@ -43,7 +45,7 @@ def _run(cmd: list) -> None:
 def build_drmctl(force: bool = False) -> str:
     src = os.path.join(PKG_DIR, "drmctl.cpp")
     out = os.path.join(PKG_DIR, "_drmctl.so")
-    if force or _needs_build(src, out):
+    if force or _needs_build(out, src):
         _run(
             ["g++", "-O2", "-std=c++17", "-shared", "-fPIC", src, "-o", out]
             + _python_includes()
@@ -51,10 +53,15 @@ def build_drmctl(force: bool = False) -> str:
     return out
 
 
+# headers shared by the probe and the sweeps
+_HIP_HEADERS = [os.path.join(PKG_DIR, h)
+                for h in ("hip_util.h", "probe_kernels.h")]
+
+
 def build_healthprobe(force: bool = False) -> str:
     src = os.path.join(PKG_DIR, "health_probe.hip")
     out = os.path.join(PKG_DIR, "_healthprobe.so")
-    if force or _needs_build(src, out):
+    if force or _needs_build(out, src, *_HIP_HEADERS):
         _run(
             [
                 HIPCC,
@@ -76,7 +83,7 @@ def build_fastserver(force: bool = False) -> str:
     src = os.path.join(PKG_DIR, "fastserver.cpp")
     out = os.path.join(PKG_DIR, "_fastserver.so")
     hdr = os.path.join(PKG_DIR, "nghttp2_abi.h")
-    if force or _needs_build(src, out) or _needs_build(hdr, out):
+    if force or _needs_build(out, src, hdr):
         _run(
             ["g++", "-O2", "-std=c++17", "-shared", "-fPIC", src, "-o", out,
              "-ldl", "-pthread"]
@@ -89,13 +96,27 @@ def build_h2tool(force: bool = False) -> str:
     src = os.path.join(PKG_DIR, "h2tool.cpp")
     out = os.path.join(PKG_DIR, "_h2tool.so")
     hdr = os.path.join(PKG_DIR, "nghttp2_abi.h")
-    if force or _needs_build(src, out) or _needs_build(hdr, out):
+    if force or _needs_build(out, src, hdr):
         _run(
             ["g++", "-O2", "-std=c++17", "-shared", "-fPIC", src, "-o", out,
              "-ldl"]
             + _python_includes()
         )
     return out
+
+
+def build_sweeps(force: bool = False) -> list:
+    """The stand-alone mfma_bench / hbm_bench binaries that measure the
+    probe's kernels against their variants; not part of build_all."""
+    outs = []
+    for name in ("mfma_bench", "hbm_bench"):
+        out = os.path.join(PKG_DIR, name)
+        src = out + ".hip"
+        if force or _needs_build(out, src, *_HIP_HEADERS):
+            _run([HIPCC, f"--offload-arch={GFX_ARCH}", "-O3", "-std=c++17",
+                  src, "-o", out])
+        outs.append(out)
+    return outs
 
 
 def build_all(force: bool = False) -> list:
@@ -107,5 +128,6 @@ if __name__ == "__main__":
     import sys
 
     force = "--force" in sys.argv
-    for so in build_all(force):
-        print(so)
+    build = build_sweeps if "--sweeps" in sys.argv else build_all
+    for built in build(force):
+        print(built)

@@ -4,23 +4,18 @@
 // check: plain float4 grid-stride vs unrolled vs nontemporal hints.
 // Guide: MI355X_MICROARCH.md §HBM (6.29 TB/s measured float4 copy ceiling).
 //
-// Build: hipcc --offload-arch=gfx950 -O3 hbm_bench.hip -o hbm_bench
+// The winner, the nontemporal one-shot, is the probe's hbm_copy_kernel and is
+// measured from probe_kernels.h; the variants it beat stay here.
+//
+// Build: python -m k8s_device_plugin_amd.native.build --sweeps  (make sweeps)
 // Run:   ./hbm_bench [bytes]
-
-#include <hip/hip_runtime.h>
 
 #include <cstdio>
 #include <cstdlib>
+#include <exception>
 
-#define HIP_CHECK(x)                                                      \
-    do {                                                                  \
-        hipError_t e = (x);                                               \
-        if (e != hipSuccess) {                                            \
-            fprintf(stderr, "HIP error %s at %s:%d\n",                    \
-                    hipGetErrorString(e), __FILE__, __LINE__);            \
-            exit(1);                                                      \
-        }                                                                 \
-    } while (0)
+#include "hip_util.h"
+#include "probe_kernels.h"
 
 __global__ void copy_plain(const float4 *__restrict__ src,
                            float4 *__restrict__ dst, size_t n) {
@@ -46,8 +41,6 @@ __global__ void copy_unroll4(const float4 *__restrict__ src,
     }
     for (; i < n; i += stride) dst[i] = src[i];
 }
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 __global__ void copy_nt(const float4 *__restrict__ src4,
                         float4 *__restrict__ dst4, size_t n) {
@@ -79,62 +72,23 @@ __global__ void copy_nt_unroll4(const float4 *__restrict__ src4,
         __builtin_nontemporal_store(__builtin_nontemporal_load(&src[i]), &dst[i]);
 }
 
-// no-loop one-shot: thread t copies exactly 4 contiguous-stride elements
-__global__ void copy_nt_oneshot(const float4 *__restrict__ src4,
-                                float4 *__restrict__ dst4, size_t n) {
-    const f32x4 *__restrict__ src = reinterpret_cast<const f32x4 *>(src4);
-    f32x4 *__restrict__ dst = reinterpret_cast<f32x4 *>(dst4);
-    size_t stride = (size_t)gridDim.x * blockDim.x;
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i + 3 * stride < n) {
-        f32x4 a = __builtin_nontemporal_load(&src[i]);
-        f32x4 b = __builtin_nontemporal_load(&src[i + stride]);
-        f32x4 c = __builtin_nontemporal_load(&src[i + 2 * stride]);
-        f32x4 d = __builtin_nontemporal_load(&src[i + 3 * stride]);
-        __builtin_nontemporal_store(a, &dst[i]);
-        __builtin_nontemporal_store(b, &dst[i + stride]);
-        __builtin_nontemporal_store(c, &dst[i + 2 * stride]);
-        __builtin_nontemporal_store(d, &dst[i + 3 * stride]);
-    } else {
-        for (; i < n; i += stride)
-            __builtin_nontemporal_store(__builtin_nontemporal_load(&src[i]), &dst[i]);
-    }
-}
-
-__global__ void fill(float4 *buf, size_t n) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (; i < n; i += stride)
-        buf[i] = make_float4((float)(i & 0xFFFF), 1.f, 2.f, 3.f);
-}
-
 template <typename K>
 double bench(K kernel, const float4 *src, float4 *dst, size_t n, int blocks,
              int threads, int iters) {
-    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), 0, 0, src, dst, n);
-    HIP_CHECK(hipDeviceSynchronize());
-    hipEvent_t t0, t1;
-    HIP_CHECK(hipEventCreate(&t0));
-    HIP_CHECK(hipEventCreate(&t1));
-    HIP_CHECK(hipEventRecord(t0));
-    for (int i = 0; i < iters; ++i)
+    auto launch = [&] {
         hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), 0, 0, src, dst, n);
-    HIP_CHECK(hipEventRecord(t1));
-    HIP_CHECK(hipEventSynchronize(t1));
-    float ms = 0;
-    HIP_CHECK(hipEventElapsedTime(&ms, t0, t1));
-    HIP_CHECK(hipEventDestroy(t0));
-    HIP_CHECK(hipEventDestroy(t1));
+    };
+    float ms = timed_ms(launch, [&] {
+        for (int i = 0; i < iters; ++i) launch();
+    });
     return (2.0 * n * sizeof(float4) * iters) / (ms * 1e6);  // GB/s
 }
 
-int main(int argc, char **argv) {
-    size_t bytes = argc > 1 ? strtoull(argv[1], nullptr, 0) : (size_t)4 << 30;
+static void sweep(size_t bytes) {
     size_t n = bytes / sizeof(float4);
-    float4 *src, *dst;
-    HIP_CHECK(hipMalloc(&src, n * sizeof(float4)));
-    HIP_CHECK(hipMalloc(&dst, n * sizeof(float4)));
-    hipLaunchKernelGGL(fill, dim3(8192), dim3(256), 0, 0, src, n);
+    DeviceBuffer<float4> src_buf(n), dst_buf(n);
+    float4 *src = src_buf.get(), *dst = dst_buf.get();
+    hipLaunchKernelGGL(fill_pattern_kernel, dim3(8192), dim3(256), 0, 0, src, n);
     HIP_CHECK(hipDeviceSynchronize());
 
     const int iters = 10;
@@ -146,19 +100,28 @@ int main(int argc, char **argv) {
         double tu = bench(copy_nt_unroll4, src, dst, n, blocks, 256, iters);
         printf("blocks=%5d plain=%7.0f unroll4=%7.0f nt=%7.0f nt_unroll4=%7.0f GB/s\n",
                blocks, p, u, t, tu);
-        if (tu > best.gbps) best = {"nt_unroll4", tu};
         if (p > best.gbps) best = {"plain", p};
         if (u > best.gbps) best = {"unroll4", u};
         if (t > best.gbps) best = {"nt", t};
         if (tu > best.gbps) best = {"nt_unroll4", tu};
     }
     {
-        // exact-fit grid: every thread does its 4 elements, no loop
+        // the probe's kernel on an exact-fit grid: every thread does its 4
+        // elements, no loop
         int blocks = (int)(n / (256 * 4));
-        double o = bench(copy_nt_oneshot, src, dst, n, blocks, 256, iters);
+        double o = bench(hbm_copy_kernel, src, dst, n, blocks, 256, iters);
         printf("oneshot blocks=%d nt_oneshot=%7.0f GB/s\n", blocks, o);
         if (o > best.gbps) best = {"nt_oneshot", o};
     }
     printf("BEST %s %.0f GB/s\n", best.name, best.gbps);
+}
+
+int main(int argc, char **argv) {
+    try {
+        sweep(argc > 1 ? strtoull(argv[1], nullptr, 0) : (size_t)4 << 30);
+    } catch (const std::exception &e) {
+        fprintf(stderr, "%s\n", e.what());
+        return 1;
+    }
     return 0;
 }

@@ -117,6 +117,26 @@ def test_deep_health_probe():
     assert degraded["floor_violations"], degraded
 
 
+@pytest.mark.parametrize("hbm_bytes", [
+    16,                        # n = 1: one thread, tail path only
+    16 * 31,                   # n = 31: sample windows overlap, none may pass n
+    16 * (3 * 262144 + 5),     # minimum 1024-block grid: 5 threads 4-wide, rest tail
+    16 * (4 * 262144 + 7),     # ceil(n/1024) blocks: 4-wide and tail threads mixed
+])
+def test_deep_probe_hbm_copy_odd_sizes(hbm_bytes):
+    """The copy's head, middle and end are checked component by component
+    at sizes where the one-shot kernel's 4-wide and tail paths mix; floors
+    are off so that only correctness decides."""
+    _require_gpu()
+    from k8s_device_plugin_amd.native import deep_health_probe
+
+    probe = deep_health_probe(device=0, hbm_bytes=hbm_bytes,
+                              mfma_floor_tflops=0, hbm_floor_gbps=0)
+    assert probe["hbm_copy_ok"], probe
+    assert probe["healthy"], probe
+    assert probe["hbm_bytes_tested"] == hbm_bytes
+
+
 def test_smoke_entry():
     _require_gpu()
     sys.path.insert(0, REPO)
