@@ -94,17 +94,68 @@ def _floor_from_env(env: str, default: float) -> float:
         return default
 
 
+CU_SWEEP_ENV = "AMDXDP_CU_SWEEP"
+CU_SWEEP_INJECT_ENV = "AMDXDP_CU_SWEEP_INJECT"
+
+
+def cu_sweep_enabled(cu_sweep: Optional[bool] = None) -> bool:
+    """An explicit argument wins; None reads AMDXDP_CU_SWEEP (unset, empty
+    or 0 = off)."""
+    if cu_sweep is not None:
+        return bool(cu_sweep)
+    return os.environ.get(CU_SWEEP_ENV, "0").strip() not in ("", "0")
+
+
+def _sweep_inject_from_env():
+    """AMDXDP_CU_SWEEP_INJECT="block:wave:pipe" -> (block, wave, pipe): the
+    sweep then simulates one bad matrix pipe on healthy hardware."""
+    spec = os.environ.get(CU_SWEEP_INJECT_ENV, "").strip()
+    if not spec:
+        return None
+    try:
+        block, wave, pipe = (int(x) for x in spec.split(":"))
+    except ValueError:
+        raise ValueError(
+            f"{CU_SWEEP_INJECT_ENV}={spec!r}: expected block:wave:pipe"
+        ) from None
+    return (block, wave, pipe)
+
+
+def cu_sweep_violations(sweep: dict) -> list:
+    """One line per SIMD that failed the sweep."""
+    return [
+        "cu_sweep: xcc {xcc} se {se} cu {cu} simd {simd} failed {pipes}".format(
+            xcc=b["xcc"], se=b["se"], cu=b["cu"], simd=b["simd"],
+            pipes=",".join(b["pipes"]),
+        )
+        for b in sweep.get("bad", [])
+    ]
+
+
+def run_cu_sweep(device: int = 0, mod=None) -> dict:
+    """Known-answer MFMA sweep of every CU and SIMD of one HIP device."""
+    if mod is None:
+        mod = load_healthprobe(required=True)
+    return mod.cu_sweep(device=device, inject=_sweep_inject_from_env())
+
+
 def deep_health_probe(
     device: int = 0,
     hbm_bytes: int = 1 << 30,
     mfma_floor_tflops: Optional[float] = None,
     hbm_floor_gbps: Optional[float] = None,
+    cu_sweep: Optional[bool] = None,
 ) -> dict:
     """Run the on-GPU MFMA/LDS/HBM probe and apply performance floors.
 
     Raises loudly when the extension is missing on a GPU machine.  The
     result's `healthy` goes False on any correctness failure OR any floor
     violation; violations are listed in `floor_violations`.
+
+    cu_sweep (None = env AMDXDP_CU_SWEEP, default off) adds the known-answer
+    MFMA sweep of every CU and SIMD under `cu_sweep`: a bad SIMD makes the
+    GPU unhealthy, with one violation line each; a sweep that could not reach
+    every SIMD but found nothing bad only sets `warnings`.
     """
     if mfma_floor_tflops is None:
         mfma_floor_tflops = _floor_from_env(MFMA_FLOOR_ENV,
@@ -127,6 +178,16 @@ def deep_health_probe(
         "mfma_tflops": mfma_floor_tflops,
         "hbm_gbps": hbm_floor_gbps,
     }
+    if cu_sweep_enabled(cu_sweep):
+        sweep = run_cu_sweep(device, mod)
+        res["cu_sweep"] = sweep
+        violations.extend(cu_sweep_violations(sweep))
+        if sweep.get("ok") and not sweep.get("coverage_complete"):
+            res["warnings"] = [
+                "cu_sweep_incomplete: {} of {} CUs, {} SIMDs".format(
+                    sweep.get("cus_covered"), sweep.get("cu_count"),
+                    sweep.get("simds_covered"))
+            ]
     res["floor_violations"] = violations
     if violations:
         res["healthy"] = False

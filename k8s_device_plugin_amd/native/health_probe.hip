@@ -8,7 +8,10 @@
 //      (v_mfma_f32_16x16x32_bf16 invariant checks, exact in bf16/f32);
 //   3. LDS write/read round-trips a full 128 KiB per CU;
 //   4. HBM sustains a float4 streaming copy at a reportable GB/s
-//      (grid sized >>256 workgroups to cover all 8 XCDs).
+//      (grid sized >>256 workgroups to cover all 8 XCDs);
+//   5. on request (cu_sweep), exact known-answer products of the bf16, f16,
+//      fp8, i8 and MX-fp8 matrix pipes on every SIMD of every CU, with the
+//      place each wave ran read from the hardware id registers.
 //
 // Used by the plugin's optional deep health check, __graft_entry__.smoke(),
 // and the gpu-marked tests.  The kernels live in probe_kernels.h (shared
@@ -18,7 +21,10 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <cstring>
+#include <map>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include <pybind11/pybind11.h>
@@ -211,6 +217,250 @@ py::dict mfma_probe_raw(int device) {
     return out;
 }
 
+// ---------------- CU sweep ----------------
+
+// Rounds a sweep launch runs when the caller passes reps = 0.  Measured on
+// MI355X (profiles/cu_sweep_mi355x.md): already reps = 1 (22 us) reached all
+// 1024 SIMDs in one launch, 35 of 35 times; 8 keeps each block alive 2.4x
+// as long (53 us) and runs every product 8 times, for 1 % of the probe's
+// 5.5 ms.
+constexpr int kSweepDefaultReps = 8;
+constexpr int kSweepMaxLaunches = 4;
+
+struct SimdId {
+    int xcc, se, sh, cu, simd;
+    bool operator<(const SimdId &o) const {
+        return std::tie(xcc, se, sh, cu, simd) <
+               std::tie(o.xcc, o.se, o.sh, o.cu, o.simd);
+    }
+};
+
+// HW_ID of GCN/CDNA: SIMD_ID 5:4, CU_ID 11:8, SH_ID 12, SE_ID 14:13 (two
+// bits from gfx942 on, 4 SEs per XCC); XCC_ID 3:0 of its own register.
+SimdId decode_hw_id(uint32_t hw_id, uint32_t xcc_id) {
+    return {(int)(xcc_id & 15), (int)(hw_id >> 13 & 3), (int)(hw_id >> 12 & 1),
+            (int)(hw_id >> 8 & 15), (int)(hw_id >> 4 & 3)};
+}
+
+py::tuple decode_hw_id_py(uint32_t hw_id, uint32_t xcc_id) {
+    SimdId id = decode_hw_id(hw_id, xcc_id);
+    return py::make_tuple(id.xcc, id.se, id.sh, id.cu, id.simd);
+}
+
+py::list sweep_pipe_names(uint32_t mask) {
+    py::list names;
+    for (int p = 0; p < cusweep::kPipes; ++p)
+        if (mask >> p & 1) names.append(cusweep::kPipeDesc[p].name);
+    return names;
+}
+
+py::dict sweep_first_failure(const SweepRecord &r) {
+    py::dict first;
+    first["pipe"] = r.first_pipe < (uint32_t)cusweep::kPipes
+                        ? cusweep::kPipeDesc[r.first_pipe].name : "?";
+    first["t"] = r.first_t;
+    first["lane"] = r.first_lane;
+    first["reg"] = r.first_reg;
+    first["got"] = r.first_got;            // result register bits
+    first["expected"] = r.first_expected;
+    return first;
+}
+
+// Known-answer MFMA products on every SIMD of every CU (cu_sweep_kernel).
+// One launch of cu_count blocks; where the records show a SIMD that no wave
+// ran on, launch again with doubled reps (longer-lived blocks overlap more
+// surely), at most kSweepMaxLaunches in all, accumulating coverage and
+// failures.  inject = (block, wave, pipe) simulates one bad pipe.
+py::dict cu_sweep(int device, int reps, py::object inject) {
+    int inj[3] = {-1, -1, -1};
+    if (!inject.is_none()) {
+        py::sequence seq = inject.cast<py::sequence>();
+        if (py::len(seq) != 3)
+            throw std::invalid_argument("inject must be (block, wave, pipe)");
+        for (int i = 0; i < 3; ++i) inj[i] = seq[i].cast<int>();
+        if (inj[0] < 0 || inj[1] < 0 || inj[1] >= 4 || inj[2] < 0 ||
+            inj[2] >= cusweep::kPipes)
+            throw std::invalid_argument(
+                "inject: block >= 0, wave in 0..3, pipe in 0.." +
+                std::to_string(cusweep::kPipes - 1));
+    }
+    if (reps < 0) throw std::invalid_argument("reps must be >= 0");
+    if (reps == 0) reps = kSweepDefaultReps;
+    if (reps > (1 << 16)) throw std::invalid_argument("reps must be <= 65536");
+
+    HIP_CHECK(hipSetDevice(device));
+    hipDeviceProp_t props;
+    HIP_CHECK(hipGetDeviceProperties(&props, device));
+    const int cu_count = props.multiProcessorCount;
+    if (inj[0] >= cu_count)
+        throw std::invalid_argument("inject: block must be below cu_count");
+    if ((size_t)cusweep::kTableBytes > props.sharedMemPerBlock)
+        throw std::runtime_error("the sweep tables do not fit this GPU's LDS");
+
+    static const std::vector<uint8_t> table = cusweep::build_table();
+    DeviceBuffer<uint4> d_table(table.size() / sizeof(uint4));
+    HIP_CHECK(hipMemcpy(d_table.get(), table.data(), table.size(),
+                        hipMemcpyHostToDevice));
+    const size_t n_rec = (size_t)cu_count * 4;
+    DeviceBuffer<SweepRecord> d_rec(n_rec);
+    std::vector<SweepRecord> h_rec(n_rec);
+
+    std::map<std::tuple<int, int, int, int>, unsigned> simds_of_cu;
+    struct Bad {
+        uint32_t pipes = 0;
+        unsigned long long lanes = 0;
+        SweepRecord first;
+    };
+    std::map<SimdId, Bad> bad;
+    py::list records;
+    double sweep_ms = 0;
+    int launches = 0, simds_covered = 0;
+    bool complete = false;
+    EventPair ev;
+    while (launches < kSweepMaxLaunches && !complete) {
+        if (launches) reps = std::min(reps * 2, 1 << 16);
+        ++launches;
+        HIP_CHECK(hipMemset(d_rec.get(), 0, n_rec * sizeof(SweepRecord)));
+        HIP_CHECK(hipEventRecord(ev.start));
+        hipLaunchKernelGGL(cu_sweep_kernel, dim3(cu_count), dim3(256),
+                           cusweep::kTableBytes, 0, d_table.get(), d_rec.get(),
+                           reps, inj[0], inj[1], inj[2]);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipEventRecord(ev.stop));
+        HIP_CHECK(hipEventSynchronize(ev.stop));
+        float ms = 0;
+        HIP_CHECK(hipEventElapsedTime(&ms, ev.start, ev.stop));
+        sweep_ms += ms;
+        HIP_CHECK(hipMemcpy(h_rec.data(), d_rec.get(),
+                            n_rec * sizeof(SweepRecord), hipMemcpyDeviceToHost));
+
+        for (const SweepRecord &r : h_rec) {
+            const unsigned long long lanes =
+                (unsigned long long)r.bad_lanes_hi << 32 | r.bad_lanes_lo;
+            records.append(py::make_tuple(
+                r.hw_id, r.xcc_id, r.fail_pipes, lanes, r.first_pipe, r.first_t,
+                r.first_lane, r.first_reg, r.first_got, r.first_expected));
+            const SimdId id = decode_hw_id(r.hw_id, r.xcc_id);
+            simds_of_cu[{id.xcc, id.se, id.sh, id.cu}] |= 1u << id.simd;
+            if (r.fail_pipes) {
+                auto it = bad.find(id);
+                if (it == bad.end()) it = bad.emplace(id, Bad{0, 0, r}).first;
+                it->second.pipes |= r.fail_pipes;
+                it->second.lanes |= lanes;
+            }
+        }
+        simds_covered = 0;
+        for (const auto &kv : simds_of_cu)
+            simds_covered += __builtin_popcount(kv.second);
+        complete = (int)simds_of_cu.size() == cu_count &&
+                   simds_covered == 4 * cu_count;
+    }
+
+    py::list bad_list, uncovered;
+    for (const auto &kv : bad) {
+        py::dict b;
+        b["xcc"] = kv.first.xcc;
+        b["se"] = kv.first.se;
+        b["sh"] = kv.first.sh;
+        b["cu"] = kv.first.cu;
+        b["simd"] = kv.first.simd;
+        b["pipes"] = sweep_pipe_names(kv.second.pipes);
+        b["bad_lanes"] = kv.second.lanes;
+        b["first"] = sweep_first_failure(kv.second.first);
+        bad_list.append(b);
+    }
+    for (const auto &kv : simds_of_cu)
+        if (kv.second != 0xF) {
+            py::dict u;
+            u["xcc"] = std::get<0>(kv.first);
+            u["se"] = std::get<1>(kv.first);
+            u["sh"] = std::get<2>(kv.first);
+            u["cu"] = std::get<3>(kv.first);
+            py::list seen;
+            for (int s = 0; s < 4; ++s)
+                if (kv.second >> s & 1) seen.append(s);
+            u["simds"] = seen;
+            uncovered.append(u);
+        }
+
+    py::dict out;
+    out["cu_count"] = cu_count;
+    out["cus_covered"] = (int)simds_of_cu.size();
+    out["simds_covered"] = simds_covered;
+    out["coverage_complete"] = complete;
+    out["launches"] = launches;
+    out["reps"] = reps;  // of the last launch
+    out["waves_checked"] = (uint64_t)n_rec * launches;
+    out["pipes"] = sweep_pipe_names((1u << cusweep::kPipes) - 1);
+    out["bad"] = bad_list;
+    out["uncovered"] = uncovered;
+    out["records"] = records;
+    out["sweep_ms"] = sweep_ms;
+    out["ok"] = bad.empty();
+    return out;
+}
+
+// The sweep's tables for the tests: no HIP call, works without a GPU.
+py::dict cu_sweep_reference() {
+    auto matrix = [](const std::vector<int> &m, int rows, int cols) {
+        py::list out;
+        for (int i = 0; i < rows; ++i) {
+            py::list row;
+            for (int j = 0; j < cols; ++j) row.append(m[(size_t)i * cols + j]);
+            out.append(row);
+        }
+        return out;
+    };
+    py::list pipes;
+    for (int p = 0; p < cusweep::kPipes; ++p) {
+        const cusweep::PipeDesc &d = cusweep::kPipeDesc[p];
+        py::list tests;
+        for (int t = 0; t < cusweep::kTests; ++t) {
+            const cusweep::TestVector v = cusweep::make_test(p, t);
+            py::list expected, expected_bits;  // [64 lanes][regs]
+            for (int l = 0; l < cusweep::kLanes; ++l) {
+                py::list vals, bits;
+                for (int r = 0; r < d.regs; ++r) {
+                    const uint32_t b = v.expected[(size_t)l * d.regs + r];
+                    bits.append(b);
+                    if (d.int_result) {
+                        vals.append((int32_t)b);
+                    } else {
+                        float f;
+                        std::memcpy(&f, &b, 4);
+                        vals.append(f);
+                    }
+                }
+                expected.append(vals);
+                expected_bits.append(bits);
+            }
+            py::dict test;
+            test["A"] = matrix(v.A, d.M, d.K);
+            test["B"] = matrix(v.B, d.K, d.N);
+            test["expected"] = expected;
+            test["expected_bits"] = expected_bits;
+            test["a_frag"] = py::bytes((const char *)v.a_frag.data(), v.a_frag.size());
+            test["b_frag"] = py::bytes((const char *)v.b_frag.data(), v.b_frag.size());
+            tests.append(test);
+        }
+        py::dict pipe;
+        pipe["name"] = d.name;
+        pipe["M"] = d.M;
+        pipe["N"] = d.N;
+        pipe["K"] = d.K;
+        pipe["regs"] = d.regs;
+        pipe["int_result"] = d.int_result;
+        pipe["tests"] = tests;
+        pipes.append(pipe);
+    }
+    py::dict out;
+    out["pipes"] = pipes;
+    out["tests_per_pipe"] = cusweep::kTests;
+    out["table_bytes"] = cusweep::kTableBytes;
+    out["default_reps"] = kSweepDefaultReps;
+    return out;
+}
+
 int device_count() {
     int n = 0;
     hipError_t e = hipGetDeviceCount(&n);
@@ -286,4 +536,9 @@ PYBIND11_MODULE(_healthprobe, m) {
     m.def("p2p_bandwidth", &p2p_bandwidth, py::arg("src") = 0,
           py::arg("dst") = 1, py::arg("bytes") = (size_t)1 << 30);
     m.def("mfma_probe_raw", &mfma_probe_raw, py::arg("device") = 0);
+    m.def("cu_sweep", &cu_sweep, py::arg("device") = 0, py::arg("reps") = 0,
+          py::arg("inject") = py::none());
+    m.def("cu_sweep_reference", &cu_sweep_reference);
+    m.def("decode_hw_id", &decode_hw_id_py, py::arg("hw_id"),
+          py::arg("xcc_id"));
 }

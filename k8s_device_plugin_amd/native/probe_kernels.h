@@ -7,6 +7,8 @@
 
 #include <cstdint>
 
+#include "sweep_table.h"
+
 namespace {  // one translation unit per binary; keep the kernels internal
 
 // ---------------- wavefront probe ----------------
@@ -152,6 +154,183 @@ __global__ void fill_pattern_kernel(float4 *buf, size_t n) {
     for (; i < n; i += stride) {
         float v = (float)(i & 0xFFFF);
         buf[i] = make_float4(v, v + 0.25f, v + 0.5f, v + 0.75f);
+    }
+}
+
+// ---------------- CU sweep: known-answer MFMA on every SIMD ----------------
+
+// One record per wave, written by that wave with plain stores; the host
+// zeroes the array before the launch.
+struct SweepRecord {
+    uint32_t hw_id;       // HW_REG_HW_ID, whole register
+    uint32_t xcc_id;      // HW_REG_XCC_ID
+    uint32_t fail_pipes;  // bit p: pipe p gave a wrong result
+    uint32_t bad_lanes_lo, bad_lanes_hi;  // OR of the mismatch ballots
+    // first failure, valid when fail_pipes != 0
+    uint32_t first_pipe, first_t, first_lane, first_reg;
+    uint32_t first_got, first_expected;
+    uint32_t reserved;
+};
+
+// where the inject hook flips its one bit
+constexpr int kSweepInjectLane = 5;
+constexpr int kSweepInjectReg = 1;
+constexpr uint32_t kSweepInjectBit = 1u << 3;
+
+using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
+using i32x4 = __attribute__((ext_vector_type(4))) int;
+using i32x8 = __attribute__((ext_vector_type(8))) int;
+
+// D = A * B + zero for pipe P (cusweep::kPipeDesc) from this lane's packed
+// fragments, as result register bits.  zero is 0 that the compiler cannot
+// see through, so the product is computed again in every round.  Vector
+// elements go through __float_as_uint: __builtin_bit_cast of o[r] read
+// element 0 for every r (hipcc 7.x), which the first hardware run showed.
+template <int P>
+__device__ inline void sweep_mfma(const unsigned char *a, const unsigned char *b,
+                                  uint32_t zero, uint32_t *d) {
+#if defined(__gfx950__)
+    constexpr int R = cusweep::kPipeDesc[P].regs;
+    const float fz = __uint_as_float(zero);
+    if constexpr (P == 1) {
+        f32x16 c;
+        for (int r = 0; r < 16; ++r) c[r] = fz;
+        f32x16 o = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+            *reinterpret_cast<const bf16x8 *>(a),
+            *reinterpret_cast<const bf16x8 *>(b), c, 0, 0, 0);
+        for (int r = 0; r < R; ++r) d[r] = __float_as_uint(o[r]);
+    } else if constexpr (P == 4) {
+        const int iz = (int)zero;
+        i32x4 c = {iz, iz, iz, iz};
+        i32x4 o = __builtin_amdgcn_mfma_i32_16x16x64_i8(
+            *reinterpret_cast<const i32x4 *>(a),
+            *reinterpret_cast<const i32x4 *>(b), c, 0, 0, 0);
+        for (int r = 0; r < R; ++r) d[r] = (uint32_t)o[r];
+    } else {
+        f32x4 c = {fz, fz, fz, fz};
+        f32x4 o;
+        if constexpr (P == 0) {
+            o = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                *reinterpret_cast<const bf16x8 *>(a),
+                *reinterpret_cast<const bf16x8 *>(b), c, 0, 0, 0);
+        } else if constexpr (P == 2) {
+            o = __builtin_amdgcn_mfma_f32_16x16x32_f16(
+                *reinterpret_cast<const f16x8 *>(a),
+                *reinterpret_cast<const f16x8 *>(b), c, 0, 0, 0);
+        } else if constexpr (P == 3) {
+            o = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(
+                *reinterpret_cast<const long *>(a),
+                *reinterpret_cast<const long *>(b), c, 0, 0, 0);
+        } else {
+            static_assert(P == 5, "six pipes");
+            // fp8 (e4m3) formats on both sides; E8M0 scale 127 = 1.0 in all
+            // four bytes of the scale register, so the byte select is moot
+            const int one = 0x7F7F7F7F;
+            o = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
+                *reinterpret_cast<const i32x8 *>(a),
+                *reinterpret_cast<const i32x8 *>(b), c, 0, 0, 0, one, 0, one);
+        }
+        for (int r = 0; r < R; ++r) d[r] = __float_as_uint(o[r]);
+    }
+#else
+    (void)a;
+    (void)b;
+    for (int r = 0; r < cusweep::kPipeDesc[P].regs; ++r) d[r] = zero;
+#endif
+}
+
+// wave-uniform running state of one wave's sweep
+struct SweepWaveState {
+    uint32_t fail_pipes = 0;
+    unsigned long long bad_lanes = 0;
+    bool have_first = false;
+};
+
+template <int P>
+__device__ inline void sweep_pipe(const unsigned char *table, int lane,
+                                  uint32_t zero, bool inject,
+                                  SweepWaveState &st, SweepRecord *rec) {
+    constexpr int FB = cusweep::frag_bytes(P), R = cusweep::kPipeDesc[P].regs;
+    for (int t = 0; t < cusweep::kTests; ++t) {
+        const unsigned char *a = table + cusweep::test_offset(P, t);
+        const unsigned char *b = a + cusweep::kLanes * FB;
+        const uint32_t *want =
+            reinterpret_cast<const uint32_t *>(b + cusweep::kLanes * FB) + lane * R;
+        uint32_t d[R];
+        sweep_mfma<P>(a + lane * FB, b + lane * FB, zero, d);
+        if (inject && lane == kSweepInjectLane) d[kSweepInjectReg] ^= kSweepInjectBit;
+        int bad_reg = -1;  // the lowest mismatching register of this lane
+        uint32_t got = 0, expected = 0;
+#pragma unroll
+        for (int r = R - 1; r >= 0; --r)
+            if (d[r] != want[r]) {
+                bad_reg = r;
+                got = d[r];
+                expected = want[r];
+            }
+        unsigned long long ballot = __ballot(bad_reg >= 0);
+        if (ballot) {
+            st.fail_pipes |= 1u << P;
+            st.bad_lanes |= ballot;
+            if (!st.have_first) {
+                st.have_first = true;
+                // the lowest bad lane reports its own registers
+                if (lane == __ffsll((long long)ballot) - 1) {
+                    rec->first_pipe = P;
+                    rec->first_t = t;
+                    rec->first_lane = lane;
+                    rec->first_reg = bad_reg;
+                    rec->first_got = got;
+                    rec->first_expected = expected;
+                }
+            }
+        }
+    }
+}
+
+// One 4-wave block per CU.  The block copies the packed operand and
+// expected-result tables (sweep_table.h) into LDS, cusweep::kTableBytes of
+// dynamic LDS: more than half of the CU's 160 KiB, so no two sweep blocks
+// share a CU.  Each wave then reads where it runs from the hardware id
+// registers, runs reps rounds of every pipe's known-answer products on its
+// SIMD and compares every result register bit for bit.  Nothing here
+// depends on where a block lands and no block waits for another; the host
+// works out the coverage from the records.
+// inject_block / inject_wave / inject_pipe (-1 = off) make that one wave
+// flip one bit of one result register of that pipe before comparing: a bad
+// pipe simulated on healthy hardware.
+__global__ void __launch_bounds__(256)
+cu_sweep_kernel(const uint4 *__restrict__ table, SweepRecord *records, int reps,
+                int inject_block, int inject_wave, int inject_pipe) {
+    extern __shared__ uint4 sweep_lds[];
+    for (int i = threadIdx.x; i < cusweep::kTableBytes / 16; i += blockDim.x)
+        sweep_lds[i] = table[i];
+    __syncthreads();
+
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    SweepRecord *rec = &records[blockIdx.x * 4 + wave];
+    const uint32_t hw_id = __builtin_amdgcn_s_getreg(4 | 31 << 11);
+    const uint32_t xcc_id = __builtin_amdgcn_s_getreg(20 | 3 << 11);
+    const bool mine = (int)blockIdx.x == inject_block && wave == inject_wave;
+    const unsigned char *tbl = reinterpret_cast<const unsigned char *>(sweep_lds);
+
+    SweepWaveState st;
+    for (int rep = 0; rep < reps; ++rep) {
+        uint32_t zero = 0;
+        asm volatile("" : "+v"(zero));
+        sweep_pipe<0>(tbl, lane, zero, mine && inject_pipe == 0, st, rec);
+        sweep_pipe<1>(tbl, lane, zero, mine && inject_pipe == 1, st, rec);
+        sweep_pipe<2>(tbl, lane, zero, mine && inject_pipe == 2, st, rec);
+        sweep_pipe<3>(tbl, lane, zero, mine && inject_pipe == 3, st, rec);
+        sweep_pipe<4>(tbl, lane, zero, mine && inject_pipe == 4, st, rec);
+        sweep_pipe<5>(tbl, lane, zero, mine && inject_pipe == 5, st, rec);
+    }
+    if (lane == 0) {
+        rec->hw_id = hw_id;
+        rec->xcc_id = xcc_id;
+        rec->fail_pipes = st.fail_pipes;
+        rec->bad_lanes_lo = (uint32_t)st.bad_lanes;
+        rec->bad_lanes_hi = (uint32_t)(st.bad_lanes >> 32);
     }
 }
 

@@ -55,6 +55,17 @@ class _ManagerCollector:
             df.add_metric([resource], len(inst.plugin._deep_failed))
         yield df
 
+        bs = GaugeMetricFamily(
+            "amdgpu_dp_deep_probe_bad_simds",
+            "SIMDs that failed the last deep-probe CU sweep, summed over "
+            "GPUs (0 while the sweep is off)",
+            labels=["resource"],
+        )
+        for resource, inst in self.manager.plugins.items():
+            bs.add_metric([resource],
+                          sum(inst.plugin._sweep_bad_simds.values()))
+        yield bs
+
         counters = {}
         for resource, inst in self.manager.plugins.items():
             if inst.native:

@@ -59,6 +59,7 @@ class AMDGPUPlugin:
         prestart_deep: bool = False,
         deep_probe_every: int = 0,
         dev_root: str = "/dev",
+        deep_cu_sweep: bool = False,
     ):
         self.resource = resource
         self.cdi_enabled = cdi_enabled
@@ -78,6 +79,12 @@ class AMDGPUPlugin:
         self.deep_probe_every = deep_probe_every
         self._deep_beat = 0
         self._deep_failed: set = set()  # dev_ids that failed the deep probe
+        # with every deep probe (heartbeat and pre-start), also run the
+        # known-answer MFMA sweep of every CU and SIMD, on EVERY HIP ordinal
+        # of the physical GPU (in CPX mode each partition is an ordinal of
+        # its own, so all XCDs are covered)
+        self.deep_cu_sweep = deep_cu_sweep
+        self._sweep_bad_simds: Dict[str, int] = {}  # dev_id -> last count
         self.dev_root = dev_root
         self.paths = paths
         self.devices: Dict[str, GPUDevice] = {}
@@ -165,8 +172,9 @@ class AMDGPUPlugin:
         if self._deep_beat % self.deep_probe_every == 0:
             self._run_deep_check()
 
-    def _hip_ordinal(self, dev: GPUDevice) -> int:
-        """HIP device ordinal for a plugin device.
+    def _hip_ordinals(self, dev: GPUDevice) -> List[int]:
+        """HIP device ordinals of a plugin device's physical GPU, in
+        ascending order (more than one in CPX mode).
 
         Primary: exact match of the device's PCI address (dev_id, format
         "dddd:bb:dd:f") against the runtime's per-ordinal PCI bus ids
@@ -180,13 +188,56 @@ class AMDGPUPlugin:
             mod = load_healthprobe(required=False)
             if mod is not None and hasattr(mod, "pci_bus_ids"):
                 want = dev.dev_id.lower().replace(".", ":")
-                for ordinal, bus in enumerate(mod.pci_bus_ids()):
-                    if bus and bus.lower().replace(".", ":") == want:
-                        return ordinal
+                found = [
+                    ordinal
+                    for ordinal, bus in enumerate(mod.pci_bus_ids())
+                    if bus and bus.lower().replace(".", ":") == want
+                ]
+                if found:
+                    return found
         except Exception:  # enumeration impossible (no GPU) -> fallback
             pass
         phys = sorted({d.dev_id for d in self.devices.values() if d.kfd_backed})
-        return phys.index(dev.dev_id)
+        return [phys.index(dev.dev_id)]
+
+    def _hip_ordinal(self, dev: GPUDevice) -> int:
+        """First HIP ordinal of the device's physical GPU."""
+        return self._hip_ordinals(dev)[0]
+
+    def _deep_probe(self, dev: GPUDevice) -> dict:
+        """The deep probe of one physical GPU: MFMA/LDS/HBM with floors on
+        its first HIP ordinal and, with deep_cu_sweep, the CU sweep on
+        every ordinal, its bad-SIMD lines merged into floor_violations."""
+        from ..native import (
+            cu_sweep_violations,
+            deep_health_probe,
+            run_cu_sweep,
+        )
+
+        if not self.deep_cu_sweep:
+            return deep_health_probe(device=self._hip_ordinal(dev))
+        ordinals = self._hip_ordinals(dev)
+        res = deep_health_probe(device=ordinals[0], cu_sweep=False)
+        res["cu_sweep"] = {}
+        bad_simds = 0
+        for ordinal in ordinals:
+            sweep = run_cu_sweep(ordinal)
+            res["cu_sweep"][ordinal] = sweep
+            bad_simds += len(sweep.get("bad", []))
+            for line in cu_sweep_violations(sweep):
+                line = f"{line} (hip device {ordinal})"
+                log.error("deep probe on %s: %s", dev.dev_id, line)
+                res["floor_violations"].append(line)
+            if sweep.get("ok") and not sweep.get("coverage_complete"):
+                log.warning(
+                    "deep probe on %s: cu_sweep reached %s of %s CUs on hip "
+                    "device %d", dev.dev_id, sweep.get("cus_covered"),
+                    sweep.get("cu_count"), ordinal,
+                )
+        self._sweep_bad_simds[dev.dev_id] = bad_simds
+        if bad_simds:
+            res["healthy"] = False
+        return res
 
     def _run_deep_check(self) -> None:
         """Deep-probe every physical GPU; failures pin the whole GPU
@@ -196,7 +247,7 @@ class AMDGPUPlugin:
             # skip rather than condemning every (synthetic) device
             log.debug("deep probe skipped: %s/kfd not present", self.dev_root)
             return
-        from ..native import NativeExtensionMissing, deep_health_probe
+        from ..native import NativeExtensionMissing
 
         seen = set()
         for dev in sorted(self.devices.values(), key=lambda d: d.id):
@@ -204,7 +255,7 @@ class AMDGPUPlugin:
                 continue
             seen.add(dev.dev_id)
             try:
-                res = deep_health_probe(device=self._hip_ordinal(dev))
+                res = self._deep_probe(dev)
             except NativeExtensionMissing as e:
                 # deployment problem, not a device problem: scream, don't flap
                 log.error("deep probe unavailable: %s", e)
@@ -278,9 +329,7 @@ class AMDGPUPlugin:
                         f"device {dev_id} failed the pre-start probe",
                     )
                 if self.prestart_deep:
-                    from ..native import deep_health_probe
-
-                    res = deep_health_probe(device=self._hip_ordinal(dev))
+                    res = self._deep_probe(dev)
                     if not res.get("healthy"):
                         import grpc
 
