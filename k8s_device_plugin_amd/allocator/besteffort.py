@@ -12,6 +12,11 @@ internal/pkg/allocator/besteffort_policy.go:88-151, device.go:255-443):
     the request;
   - the candidate with the minimum total pairwise weight wins.
 
+There is one search (_search) with two scorers: per group in closed form
+when every partition pair of the same two GPUs weighs the same, per node
+otherwise.  native/pref_alloc.h is the same search in C++ for the native
+server; the differential tests hold the two to identical id lists.
+
 The pair weights themselves are hive-aware (weights.py), which on an
 8*MI355X node packs 2/4/8-GPU requests onto one xGMI hive.
 """
@@ -38,21 +43,6 @@ class _Group:
     dev_id: str
     parent_id: str
     node_ids: List[int]  # ascending
-
-
-@dataclass
-class _Subset:
-    ids: List[int]
-    parents: frozenset
-    weight: int
-
-    def extended(self, node_id: int, parent_idx: int,
-                 weights: Dict[int, Dict[int, int]]) -> "_Subset":
-        w = self.weight
-        for other in self.ids:
-            frm, to = (other, node_id) if other < node_id else (node_id, other)
-            w += weights.get(frm, {}).get(to, 0)
-        return _Subset(self.ids + [node_id], self.parents | {parent_idx}, w)
 
 
 class BestEffortPolicy:
@@ -113,11 +103,10 @@ class BestEffortPolicy:
         devID, link type, NUMA, hive — weights.py), so every partition
         pair of the same two physical GPUs normally scores identically.
         When that holds for the loaded topology (verified here, never
-        assumed), candidate scoring collapses to per-group counts —
-        O(G) per group addition instead of O(|subset|) per node — with
-        byte-identical results (same totals, same generation order, same
-        first-minimum tie-break).  Mirrors the native server's fast path
-        (native/fastserver.cpp AllocState::build_uniform_table).
+        assumed), allocate() scores with _uniform_scorer, else with
+        _per_node_scorer; the totals, and so the results, are identical.
+        Same check as AllocState::build_uniform_table in
+        native/pref_alloc.h.
         """
         self._uniform = True
         self._gw: Dict[str, Dict[str, int]] = {}
@@ -191,101 +180,13 @@ class BestEffortPolicy:
 
         available = [self._devices[i] for i in available_ids if i in self._devices]
         required = [self._devices[i] for i in required_ids if i in self._devices]
-        if self._uniform:
-            return self._allocate_uniform(available, required, size)
-        candidates = self._candidate_subsets(available, required, size)
-        if not candidates:
-            raise AllocationError("no candidate subset found with matching criteria")
-
-        best = min(candidates, key=lambda s: s.weight)
-        by_node = {d.node_id: d.id for d in available}
-        return [by_node[nid] for nid in best.ids if nid in by_node]
-
-    def _allocate_uniform(self, available, required, size) -> List[str]:
-        """Closed-form search under verified-uniform group-pair weights.
-
-        BFS invariant: an incomplete state has consumed every added group
-        FULLY, so a state is (parent set, add order, size, weight,
-        per-group rowsums); adding m nodes of group b costs
-        m*rowsum[b] + C(m,2)*gw[b][b].  Enumeration order, totals, and
-        the first-strict-minimum tie-break match _candidate_subsets
-        exactly (cross-checked by the oracle and differential-fuzz
-        suites); the winner's id list is reconstructed in generation
-        order with required ids appended last, as the generic path does.
-        """
         groups = self._filtered_groups(available, required)
-        new_size = size - len(required)
         req_nodes = [d.node_id for d in required]
-        gkeys = [g.dev_id for g in groups]
-        gw = self._gw
-
-        def add_group(st, fidx, m):
-            parents, order, sz, weight, rowsum = st
-            b = gkeys[fidx]
-            weight += m * rowsum.get(b, 0) + m * (m - 1) // 2 * gw[b][b]
-            rowsum = dict(rowsum)
-            for h, wbh in gw[b].items():
-                rowsum[h] = rowsum.get(h, 0) + m * wbh
-            return (parents | (1 << fidx), order + (fidx,), sz + m,
-                    weight, rowsum)
-
-        def finish_weight(st):
-            _, _, _, weight, rowsum = st
-            rowsum = dict(rowsum)
-            for rn in req_nodes:
-                b = self._group_of_node[rn]
-                weight += rowsum.get(b, 0)
-                for h, wbh in gw[b].items():
-                    rowsum[h] = rowsum.get(h, 0) + wbh
-            return weight
-
-        best = None  # (weight, order)
-        queue = []
-        seen = set()
-        for idx, g in enumerate(groups):
-            take = min(len(g.node_ids), new_size)
-            st = add_group((0, (), 0, 0, {}), idx, take)
-            if st[2] == new_size:
-                w = finish_weight(st)
-                if best is None or w < best[0]:
-                    best = (w, st[1])
-            else:
-                seen.add(st[0])
-                queue.append(st)
-        qi = 0
-        n_groups = len(groups)
-        while qi < len(queue):
-            cur = queue[qi]
-            qi += 1
-            if bin(cur[0]).count("1") == n_groups:
-                continue
-            for idx in range(n_groups):
-                if cur[0] & (1 << idx):
-                    continue
-                take = min(len(groups[idx].node_ids), new_size - cur[2])
-                st = add_group(cur, idx, take)
-                if st[2] == new_size:
-                    w = finish_weight(st)
-                    if best is None or w < best[0]:
-                        best = (w, st[1])
-                elif st[0] not in seen:
-                    seen.add(st[0])
-                    queue.append(st)
-        if best is None:
-            raise AllocationError("no candidate subset found with matching criteria")
-
+        make_scorer = self._uniform_scorer if self._uniform else self._per_node_scorer
+        nodes = _search(groups, size - len(required), req_nodes,
+                        make_scorer(groups, req_nodes))
         by_node = {d.node_id: d.id for d in available}
-        out: List[str] = []
-        remaining = new_size
-        for fidx in best[1]:
-            if remaining <= 0:
-                break
-            ids = groups[fidx].node_ids
-            take = min(len(ids), remaining)
-            out.extend(by_node[n] for n in ids[:take] if n in by_node)
-            remaining -= take
-        out.extend(by_node[n] for n in req_nodes if n in by_node)
-        return out
+        return [by_node[n] for n in nodes if n in by_node]
 
     # ---- internals ----
 
@@ -302,66 +203,111 @@ class BestEffortPolicy:
         groups.sort(key=lambda g: (len(g.node_ids), g.parent_id))
         return groups
 
-    def _candidate_subsets(
-        self,
-        available: Sequence[GPUDevice],
-        required: Sequence[GPUDevice],
-        size: int,
-    ) -> List[_Subset]:
-        groups = self._filtered_groups(available, required)
-        new_size = size - len(required)
-        req_node_ids = [d.node_id for d in required]
+    # A scorer is (extra of the empty state, add, finish): add(st, fidx, m)
+    # gives (weight, extra) of st plus the first m nodes of filtered group
+    # fidx; finish(st) gives a complete state's weight with the required
+    # nodes added.
 
-        def finish(s: _Subset) -> _Subset:
-            for rid in req_node_ids:
-                s = s.extended(rid, -1, self._weights)
-            return s
+    def _uniform_scorer(self, groups, req_nodes):
+        """Closed form under verified-uniform group-pair weights: with
+        rowsum[b] = sum_h count[h]*gw[b][h] carried as the state's extra,
+        adding m nodes of group b costs m*rowsum[b] + C(m,2)*gw[b][b] —
+        O(G) per group instead of O(|subset|) per node, same totals."""
+        gkeys = [g.dev_id for g in groups]
+        gw = self._gw
+        group_of_node = self._group_of_node
 
-        final: List[_Subset] = []
-        queue: List[_Subset] = []
+        def add_row(rowsum, b, m):
+            rowsum = dict(rowsum)
+            for h, wbh in gw[b].items():
+                rowsum[h] = rowsum.get(h, 0) + m * wbh
+            return rowsum
 
-        for idx, g in enumerate(groups):
-            s = _Subset([g.node_ids[0]], frozenset([idx]), 0)
-            if new_size == 1:
-                final.append(finish(s))
-                continue
-            fulfilled = False
-            for nid in g.node_ids[1:]:
-                s = s.extended(nid, idx, self._weights)
-                if len(s.ids) == new_size:
-                    fulfilled = True
-                    break
-            if fulfilled:
-                final.append(finish(s))
-            else:
-                queue.append(s)
+        def add(st, fidx, m):
+            b = gkeys[fidx]
+            rowsum = st[4]
+            weight = st[3] + m * rowsum.get(b, 0) + m * (m - 1) // 2 * gw[b][b]
+            return weight, add_row(rowsum, b, m)
 
-        # breadth-first extension across GPUs for requests no single GPU
-        # can satisfy (reference: device.go:406-441).  An incomplete queue
-        # state always holds ALL free devices of each parent group, so its
-        # id set — and total weight — is fully determined by the parent
-        # SET; the reference re-expands every parent-order permutation
-        # (O(G!) states), we dedupe on the set (O(2^G)), which makes
-        # 64-partition CPX requests tractable without changing any result.
-        seen_parent_sets = {s.parents for s in queue}
-        qi = 0
-        while qi < len(queue):
-            cur = queue[qi]
-            qi += 1
-            if len(cur.parents) == len(groups):
-                continue
-            for idx, g in enumerate(groups):
-                if idx in cur.parents:
-                    continue
-                s = _Subset(cur.ids, cur.parents | {idx}, cur.weight)
-                done = False
-                for nid in g.node_ids:
-                    s = s.extended(nid, idx, self._weights)
-                    if len(s.ids) == new_size:
-                        final.append(finish(s))
-                        done = True
-                        break
-                if not done and s.parents not in seen_parent_sets:
-                    seen_parent_sets.add(s.parents)
-                    queue.append(s)
-        return final
+        def finish(st):
+            weight, rowsum = st[3], st[4]
+            for rn in req_nodes:
+                b = group_of_node[rn]
+                weight += rowsum.get(b, 0)
+                rowsum = add_row(rowsum, b, 1)
+            return weight
+
+        return {}, add, finish
+
+    def _per_node_scorer(self, groups, req_nodes):
+        """Exact for any weight table: each new node is scored against
+        every node already in the state and the earlier new ones."""
+        weights = self._weights
+
+        def score(st, new_nodes):
+            nodes = _state_nodes(groups, st[1], st[2])
+            w = st[3]
+            for n in new_nodes:
+                for o in nodes:
+                    frm, to = (o, n) if o < n else (n, o)
+                    w += weights.get(frm, {}).get(to, 0)
+                nodes.append(n)
+            return w
+
+        return (None,
+                lambda st, fidx, m: (score(st, groups[fidx].node_ids[:m]), None),
+                lambda st: score(st, req_nodes))
+
+
+def _state_nodes(groups: List[_Group], order, size: int) -> List[int]:
+    """A state's nodes: its groups in add order, the last one as a prefix."""
+    nodes: List[int] = []
+    for fidx in order:
+        nodes.extend(groups[fidx].node_ids[:size - len(nodes)])
+    return nodes
+
+
+def _search(groups: List[_Group], new_size: int, req_nodes: List[int],
+            scorer) -> List[int]:
+    """Seed one state per group, extend breadth-first across groups for
+    requests no single GPU can satisfy (reference: device.go:406-441) and
+    return the nodes of the first strict-minimum complete state in
+    generation order, required nodes last.
+
+    A state is (parent bitset, group add order, size, weight, scorer's
+    extra).  An incomplete state holds ALL free nodes of every group it
+    added, so it is fully determined by the parent SET; the reference
+    re-expands every parent-order permutation (O(G!) states), we dedupe on
+    the set (O(2^G)), which makes 64-partition CPX requests tractable
+    without changing any result.
+    """
+    empty, add, finish = scorer
+    n_groups = len(groups)
+    best = None  # (weight, order)
+    queue: list = []
+    seen = set()
+
+    def extend(st, idx):
+        nonlocal best
+        take = min(len(groups[idx].node_ids), new_size - st[2])
+        weight, extra = add(st, idx, take)
+        st = (st[0] | (1 << idx), st[1] + (idx,), st[2] + take, weight, extra)
+        if st[2] == new_size:
+            w = finish(st)
+            if best is None or w < best[0]:
+                best = (w, st[1])
+        elif st[0] not in seen:
+            seen.add(st[0])
+            queue.append(st)
+
+    for idx in range(n_groups):
+        extend((0, (), 0, 0, empty), idx)
+    for cur in queue:  # grows while it is walked
+        if bin(cur[0]).count("1") == n_groups:
+            continue
+        for idx in range(n_groups):
+            if not cur[0] & (1 << idx):
+                extend(cur, idx)
+    if best is None:
+        raise AllocationError("no candidate subset found with matching criteria")
+    return _state_nodes(groups, best[1], new_size) + req_nodes

@@ -80,11 +80,14 @@ def build_healthprobe(force: bool = False) -> str:
     return out
 
 
+_FASTSERVER_HEADERS = [os.path.join(PKG_DIR, h)
+                       for h in ("nghttp2_abi.h", "pref_alloc.h")]
+
+
 def build_fastserver(force: bool = False) -> str:
     src = os.path.join(PKG_DIR, "fastserver.cpp")
     out = os.path.join(PKG_DIR, "_fastserver.so")
-    hdr = os.path.join(PKG_DIR, "nghttp2_abi.h")
-    if force or _needs_build(out, src, hdr):
+    if force or _needs_build(out, src, *_FASTSERVER_HEADERS):
         _run(
             ["g++", "-O2", "-std=c++17", "-shared", "-fPIC", src, "-o", out,
              "-ldl", "-pthread"]

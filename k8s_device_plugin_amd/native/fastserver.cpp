@@ -5,9 +5,9 @@
 // discovery/health/lifecycle and pushes PRE-SERIALIZED state (device list
 // bytes, per-device Allocate fragments, allocator tables); this server
 // owns the wire: HTTP/2 via the system libnghttp2 (dlopen, nghttp2_abi.h),
-// gRPC framing, request parsing and the preferred-allocation search — no
-// Python in the request path, so Allocate latency is the kernel's UDS
-// round trip plus microseconds of C++.
+// gRPC framing, request parsing and the preferred-allocation search
+// (pref_alloc.h) — no Python in the request path, so Allocate latency is
+// the kernel's UDS round trip plus microseconds of C++.
 //
 // Protocol surface (identical to the Python grpc server, conformance-tested
 // against the Python grpc client in tests/test_fastserver.py):
@@ -33,7 +33,6 @@
 #include <map>
 #include <memory>
 #include <mutex>
-#include <set>
 #include <string>
 #include <thread>
 #include <unordered_map>
@@ -43,8 +42,11 @@
 #include <pybind11/stl.h>
 
 #include "nghttp2_abi.h"
+#include "pref_alloc.h"
 
 namespace py = pybind11;
+using prefalloc::AllocState;
+using prefalloc::preferred_alloc;
 
 namespace {
 
@@ -116,302 +118,6 @@ std::string grpc_frame(const std::string &msg) {
     out.append((const char *)&n, 4);
     out += msg;
     return out;
-}
-
-// ---------------- native preferred-allocation search ----------------
-// Mirrors allocator/besteffort.py exactly (same grouping, ordering, seeds,
-// BFS with parent-set dedup); cross-validated in tests/test_fastserver.py.
-
-struct AllocState {
-    std::unordered_map<std::string, int> node_of_id;
-    std::unordered_map<int, std::string> id_of_node;
-    // (group sort key = parent id, member node ids ascending)
-    std::vector<std::pair<std::string, std::vector<int>>> groups;
-    std::unordered_map<uint64_t, int> weights;  // (min<<32|max) -> weight
-    bool ready = false;
-
-    // Uniform group-pair weight table: the reference's weight model
-    // derives a pair's score from per-GPU facts (same devID, link type,
-    // NUMA — device.go:136-158), so every partition pair of the same two
-    // physical GPUs scores identically.  When that uniformity actually
-    // holds in the loaded topology (verified below, not assumed), the
-    // search can score candidates from per-group counts in O(G) per
-    // extension instead of O(|subset|) — exact, same totals, same
-    // tie-break order.  Any non-uniform pair (e.g. a partition missing a
-    // link entry while its siblings have one) disables the fast path.
-    bool uniform = false;
-    std::vector<std::vector<long>> gw;       // [group][group] pair weight
-    std::unordered_map<int, int> group_of_node;
-
-    int weight(int a, int b) const {
-        if (a > b) std::swap(a, b);
-        auto it = weights.find(((uint64_t)(uint32_t)a << 32) | (uint32_t)b);
-        return it == weights.end() ? 0 : it->second;
-    }
-
-    void build_uniform_table() {
-        size_t G = groups.size();
-        group_of_node.clear();
-        for (size_t g = 0; g < G; ++g)
-            for (int n : groups[g].second) group_of_node[n] = (int)g;
-        gw.assign(G, std::vector<long>(G, 0));
-        uniform = true;
-        for (size_t a = 0; a < G && uniform; ++a) {
-            for (size_t b = a; b < G && uniform; ++b) {
-                bool first = true;
-                long w0 = 0;
-                for (int i : groups[a].second) {
-                    for (int j : groups[b].second) {
-                        if (a == b && i >= j) continue;
-                        long w = weight(i, j);
-                        if (first) { w0 = w; first = false; }
-                        else if (w != w0) { uniform = false; break; }
-                    }
-                    if (!uniform) break;
-                }
-                gw[a][b] = gw[b][a] = w0;
-            }
-        }
-    }
-};
-
-struct Subset {
-    std::vector<int> ids;
-    uint64_t parents = 0;  // bitset over filtered-group indices (<=64 groups)
-    long weight = 0;
-};
-
-bool preferred_alloc(const AllocState &st,
-                     const std::vector<std::string> &available,
-                     const std::vector<std::string> &required, int size,
-                     std::vector<std::string> &out, std::string &err) {
-    if (!st.ready) { err = "allocator not initialized"; return false; }
-    if (size <= 0) { err = "allocation size must be a positive integer"; return false; }
-    if ((int)available.size() < size) { err = "available devices count less than allocation size"; return false; }
-    if ((int)required.size() > size) { err = "must-include set larger than allocation size"; return false; }
-    if (required.size() > available.size()) { err = "must-include set larger than available set"; return false; }
-    if ((int)available.size() == size) { out = available; return true; }
-    if ((int)required.size() == size) { out = required; return true; }
-    std::set<std::string> avail_set(available.begin(), available.end());
-    for (auto &r : required)
-        if (!avail_set.count(r)) { err = "must-include devices not all available"; return false; }
-
-    std::set<int> avail_nodes, req_nodes;
-    std::vector<int> req_node_list;
-    for (auto &a : available) {
-        auto it = st.node_of_id.find(a);
-        if (it != st.node_of_id.end()) avail_nodes.insert(it->second);
-    }
-    for (auto &r : required) {
-        auto it = st.node_of_id.find(r);
-        if (it != st.node_of_id.end()) {
-            req_nodes.insert(it->second);
-            req_node_list.push_back(it->second);
-        }
-    }
-
-    // filtered groups, sorted by (len asc, parent key asc)
-    std::vector<std::pair<std::string, std::vector<int>>> groups;
-    for (auto &g : st.groups) {
-        std::vector<int> ids;
-        for (int n : g.second)
-            if (avail_nodes.count(n) && !req_nodes.count(n)) ids.push_back(n);
-        if (!ids.empty()) groups.emplace_back(g.first, std::move(ids));
-    }
-    // stable: Python's sort is stable, and equal (size, parent) keys must
-    // tie-break identically for result parity
-    std::stable_sort(groups.begin(), groups.end(),
-                     [](auto &a, auto &b) {
-                         if (a.second.size() != b.second.size())
-                             return a.second.size() < b.second.size();
-                         return a.first < b.first;
-                     });
-    if (groups.size() > 64) { err = "too many device groups"; return false; }
-
-    int new_size = size - (int)req_node_list.size();
-
-    const size_t n_orig = st.groups.size();
-    if (st.uniform && n_orig <= 64) {
-        // ---- closed-form fast path (exact under verified uniformity) ----
-        //
-        // BFS invariant: every group added to an incomplete state is
-        // consumed FULLY (the per-group loop only stops early when the
-        // request completes), so an intermediate state is fully described
-        // by (parent set, group add order, total size, weight).  Adding m
-        // nodes of group b to a state with per-group counts c[] costs
-        //   m * sum_h c[h]*gw[b][h]  +  C(m,2)*gw[b][b]
-        // — O(G) per GROUP instead of O(|subset|) per NODE, with no heap
-        // per state.  Candidate id lists are reconstructed only for the
-        // single winner, preserving the exact generation/insertion order
-        // of the general path (seed group ascending, then groups in added
-        // order, last group as a prefix, required ids appended last).
-        struct FS {
-            uint64_t parents = 0;
-            long weight = 0;
-            int size = 0;
-            uint8_t norder = 0;
-            uint8_t order[64];            // filtered group idx, add order
-            long rowsum[64];              // sum_h c[h]*gw[b][h] per ORIG b
-        };
-        // map filtered idx -> original group idx
-        std::vector<int> orig_of(groups.size());
-        {
-            std::unordered_map<std::string, int> orig_idx;
-            for (size_t i = 0; i < st.groups.size(); ++i)
-                orig_idx[st.groups[i].first] = (int)i;
-            // parent key may repeat only if dev_ids collide — they don't
-            for (size_t i = 0; i < groups.size(); ++i) {
-                // find by first member node (parent keys can be "")
-                orig_of[i] = st.group_of_node.at(groups[i].second[0]);
-            }
-        }
-        auto add_group = [&](FS &s, size_t fidx, int m) {
-            int b = orig_of[fidx];
-            s.weight += (long)m * s.rowsum[b] +
-                        (long)m * (m - 1) / 2 * st.gw[b][b];
-            for (size_t h = 0; h < n_orig; ++h)
-                s.rowsum[h] += (long)m * st.gw[b][h];
-            s.parents |= 1ull << fidx;
-            s.order[s.norder++] = (uint8_t)fidx;
-            s.size += m;
-        };
-        auto add_required = [&](FS &s) {
-            for (int rn : req_node_list) {
-                int b = st.group_of_node.at(rn);
-                s.weight += s.rowsum[b];
-                for (size_t h = 0; h < n_orig; ++h)
-                    s.rowsum[h] += st.gw[b][h];
-            }
-        };
-
-        std::vector<FS> queue;
-        queue.reserve(groups.size() <= 16 ? (1u << groups.size())
-                                          : 4096);
-        // parent-set dedup: direct bitmap when 2^G fits, else a set
-        std::vector<bool> seen_bm;
-        std::set<uint64_t> seen_set;
-        const bool use_bm = groups.size() <= 20;
-        if (use_bm) seen_bm.assign(1u << groups.size(), false);
-        auto seen_test_set = [&](uint64_t p) {
-            if (use_bm) {
-                if (seen_bm[p]) return true;
-                seen_bm[p] = true;
-                return false;
-            }
-            return !seen_set.insert(p).second;
-        };
-        // track the best final on the fly (first strict minimum, same
-        // tie-break as collecting then scanning) — avoids storing finals
-        FS best{};
-        bool have_best = false;
-        auto emit_final = [&](FS s) {
-            add_required(s);
-            if (!have_best || s.weight < best.weight) {
-                best = s;
-                have_best = true;
-            }
-        };
-        for (size_t idx = 0; idx < groups.size(); ++idx) {
-            FS s{};
-            int take = std::min((int)groups[idx].second.size(), new_size);
-            add_group(s, idx, take);
-            if (s.size == new_size) emit_final(s);
-            else { seen_test_set(s.parents); queue.push_back(s); }
-        }
-        for (size_t qi = 0; qi < queue.size(); ++qi) {
-            FS cur = queue[qi];
-            if (__builtin_popcountll(cur.parents) == (int)groups.size())
-                continue;
-            for (size_t idx = 0; idx < groups.size(); ++idx) {
-                if (cur.parents & (1ull << idx)) continue;
-                FS s = cur;
-                int take = std::min((int)groups[idx].second.size(),
-                                    new_size - s.size);
-                add_group(s, idx, take);
-                if (s.size == new_size) emit_final(s);
-                else if (!seen_test_set(s.parents)) {
-                    queue.push_back(s);
-                }
-            }
-        }
-        if (!have_best) { err = "no candidate subset found"; return false; }
-        // reconstruct the winner's id list in generation order
-        int remaining = new_size;
-        for (int oi = 0; oi < best.norder && remaining > 0; ++oi) {
-            const auto &g = groups[best.order[oi]].second;
-            int take = std::min((int)g.size(), remaining);
-            for (int i = 0; i < take; ++i) {
-                auto it = st.id_of_node.find(g[i]);
-                if (it != st.id_of_node.end()) out.push_back(it->second);
-            }
-            remaining -= take;
-        }
-        for (int rn : req_node_list) {
-            auto it = st.id_of_node.find(rn);
-            if (it != st.id_of_node.end()) out.push_back(it->second);
-        }
-        return true;
-    }
-
-    // ---- general path (non-uniform weights): per-node extension ----
-    auto extend = [&](Subset s, int nid, int parent_idx) {
-        for (int other : s.ids) s.weight += st.weight(other, nid);
-        s.ids.push_back(nid);
-        if (parent_idx >= 0) s.parents |= (1ull << parent_idx);
-        return s;
-    };
-    auto finish = [&](Subset s) {
-        for (int rn : req_node_list) s = extend(std::move(s), rn, -1);
-        return s;
-    };
-
-    std::vector<Subset> final_sets, queue;
-    std::set<uint64_t> seen;
-    for (size_t idx = 0; idx < groups.size(); ++idx) {
-        Subset s;
-        s.ids.push_back(groups[idx].second[0]);
-        s.parents = 1ull << idx;
-        if (new_size == 1) { final_sets.push_back(finish(s)); continue; }
-        bool fulfilled = false;
-        for (size_t i = 1; i < groups[idx].second.size(); ++i) {
-            s = extend(std::move(s), groups[idx].second[i], (int)idx);
-            if ((int)s.ids.size() == new_size) { fulfilled = true; break; }
-        }
-        if (fulfilled) final_sets.push_back(finish(s));
-        else { seen.insert(s.parents); queue.push_back(std::move(s)); }
-    }
-    for (size_t qi = 0; qi < queue.size(); ++qi) {
-        Subset cur = queue[qi];
-        if (__builtin_popcountll(cur.parents) == (int)groups.size()) continue;
-        for (size_t idx = 0; idx < groups.size(); ++idx) {
-            if (cur.parents & (1ull << idx)) continue;
-            Subset s = cur;
-            s.parents |= 1ull << idx;
-            bool done = false;
-            for (int nid : groups[idx].second) {
-                s = extend(std::move(s), nid, (int)idx);
-                if ((int)s.ids.size() == new_size) {
-                    final_sets.push_back(finish(s));
-                    done = true;
-                    break;
-                }
-            }
-            if (!done && !seen.count(s.parents)) {
-                seen.insert(s.parents);
-                queue.push_back(std::move(s));
-            }
-        }
-    }
-    if (final_sets.empty()) { err = "no candidate subset found"; return false; }
-    const Subset *best = &final_sets[0];
-    for (auto &s : final_sets)
-        if (s.weight < best->weight) best = &s;
-    for (int nid : best->ids) {
-        auto it = st.id_of_node.find(nid);
-        if (it != st.id_of_node.end() && avail_set.count(it->second))
-            out.push_back(it->second);
-    }
-    return true;
 }
 
 // ---------------- server ----------------
@@ -501,25 +207,7 @@ class Server {
         const std::map<std::string, int> &node_of_id,
         const std::vector<std::tuple<int, int, int>> &weights) {
         std::lock_guard<std::mutex> g(mu_);
-        alloc_.groups = groups;
-        alloc_.node_of_id.clear();
-        alloc_.id_of_node.clear();
-        for (auto &kv : node_of_id) {
-            alloc_.node_of_id[kv.first] = kv.second;
-            alloc_.id_of_node[kv.second] = kv.first;
-        }
-        alloc_.weights.clear();
-        for (auto &t : weights) {
-            int a = std::get<0>(t), b = std::get<1>(t);
-            if (a > b) std::swap(a, b);
-            alloc_.weights[((uint64_t)(uint32_t)a << 32) | (uint32_t)b] =
-                std::get<2>(t);
-        }
-        // weights may legitimately be empty: on a no-links topology
-        // (1-kfd-visible box) the policy degrades to uniform weights and
-        // every pair lookup scores 0 — the search is still well-defined
-        alloc_.ready = !alloc_.groups.empty();
-        alloc_.build_uniform_table();
+        alloc_.load(groups, node_of_id, weights);
     }
 
     void start() {
@@ -546,7 +234,7 @@ class Server {
         if (!running_.exchange(false)) return;
         wake();
         if (loop_.joinable()) loop_.join();
-        for (auto &c : conns_) destroy_conn(c.get(), false);
+        for (auto &c : conns_) destroy_conn(c.get());
         conns_.clear();
         if (listen_fd_ >= 0) ::close(listen_fd_);
         ::close(wake_pipe_[0]);
@@ -674,28 +362,19 @@ class Server {
         // only /dev/kfd).
         std::string msg;
         if (!st->req_body.empty()) {
-            if (st->req_body.size() < 5) {
-                st->grpc_status = "13";  // INTERNAL: truncated frame prefix
-                st->grpc_message = "malformed grpc frame: short prefix";
-                submit_unary(conn, stream_id, st, "", false);
-                return;
-            }
+            if (st->req_body.size() < 5)  // INTERNAL: truncated frame prefix
+                return submit_error(conn, stream_id, st, "13",
+                                    "malformed grpc frame: short prefix");
             uint8_t compressed = (uint8_t)st->req_body[0];
             uint32_t len;
             memcpy(&len, st->req_body.data() + 1, 4);
             len = ntohl(len);
-            if (compressed != 0) {
-                st->grpc_status = "12";  // UNIMPLEMENTED: compression
-                st->grpc_message = "grpc message compression not supported";
-                submit_unary(conn, stream_id, st, "", false);
-                return;
-            }
-            if (st->req_body.size() < (size_t)5 + len) {
-                st->grpc_status = "13";  // INTERNAL: truncated body
-                st->grpc_message = "malformed grpc frame: truncated body";
-                submit_unary(conn, stream_id, st, "", false);
-                return;
-            }
+            if (compressed != 0)  // UNIMPLEMENTED: compression
+                return submit_error(conn, stream_id, st, "12",
+                                    "grpc message compression not supported");
+            if (st->req_body.size() < (size_t)5 + len)  // INTERNAL
+                return submit_error(conn, stream_id, st, "13",
+                                    "malformed grpc frame: truncated body");
             msg = st->req_body.substr(5, len);
         }
 
@@ -708,14 +387,10 @@ class Server {
         } else if (p == "/v1beta1.DevicePlugin/PreStartContainer") {
             n_prestart_.fetch_add(1, std::memory_order_relaxed);
             std::string bad;
-            if (!handle_prestart(msg, bad)) {
-                st->grpc_status = "9";  // FAILED_PRECONDITION
-                st->grpc_message =
-                    "device " + bad + " failed the pre-start probe";
-                submit_unary(conn, stream_id, st, "", false);
-                return;
-            }
-            resp = "";
+            if (!handle_prestart(msg, bad))  // FAILED_PRECONDITION
+                return submit_error(
+                    conn, stream_id, st, "9",
+                    "device " + bad + " failed the pre-start probe");
         } else if (p == "/v1beta1.DevicePlugin/Allocate") {
             n_allocate_.fetch_add(1, std::memory_order_relaxed);
             auto t0 = std::chrono::steady_clock::now();
@@ -733,13 +408,8 @@ class Server {
                 (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(
                     std::chrono::steady_clock::now() - t0).count(),
                 std::memory_order_relaxed);
-            if (!ok) {
-                st->grpc_status = "3";  // INVALID_ARGUMENT
-                st->grpc_message = err;
-                resp.clear();
-                submit_unary(conn, stream_id, st, "", /*with_body=*/false);
-                return;
-            }
+            if (!ok)  // INVALID_ARGUMENT
+                return submit_error(conn, stream_id, st, "3", err);
         } else if (p == "/v1beta1.DevicePlugin/ListAndWatch") {
             n_listwatch_.fetch_add(1, std::memory_order_relaxed);
             st->is_listwatch = true;
@@ -748,15 +418,21 @@ class Server {
                 st->out = grpc_frame(list_bytes_);
                 st->out_off = 0;
             }
-            submit_stream_response(conn, stream_id, st);
+            submit_headers_common(conn, stream_id, st);
             return;
         } else {
             n_unknown_.fetch_add(1, std::memory_order_relaxed);
-            st->grpc_status = "12";  // UNIMPLEMENTED
-            submit_unary(conn, stream_id, st, "", false);
-            return;
+            return submit_error(conn, stream_id, st, "12", "");  // UNIMPLEMENTED
         }
         submit_unary(conn, stream_id, st, resp, true);
+    }
+
+    // trailers-only style failure: no message body, status in the trailer
+    void submit_error(Conn *conn, int32_t stream_id, Stream *st,
+                      const char *status, const std::string &message) {
+        st->grpc_status = status;
+        st->grpc_message = message;
+        submit_unary(conn, stream_id, st, "", false);
     }
 
     void submit_headers_common(Conn *conn, int32_t stream_id, Stream *st) {
@@ -782,10 +458,6 @@ class Server {
             st->out = with_body ? grpc_frame(msg) : std::string();
             st->out_off = 0;
         }
-        submit_headers_common(conn, stream_id, st);
-    }
-
-    void submit_stream_response(Conn *conn, int32_t stream_id, Stream *st) {
         submit_headers_common(conn, stream_id, st);
     }
 
@@ -916,14 +588,13 @@ class Server {
         }
     }
 
-    void destroy_conn(Conn *c, bool erase) {
+    void destroy_conn(Conn *c) {
         auto &ng = NgHttp2::get();
         if (c->session) ng.session_del(c->session);
         if (c->fd >= 0) ::close(c->fd);
         c->session = nullptr;
         c->fd = -1;
         c->dead = true;
-        (void)erase;
     }
 
     // returns false when the connection died
@@ -1015,7 +686,7 @@ class Server {
                 ++pi;
                 if (c->dead) continue;
                 if (rev & (POLLERR | POLLHUP)) {
-                    destroy_conn(c.get(), true);
+                    destroy_conn(c.get());
                     continue;
                 }
                 if (rev & POLLIN) {
@@ -1024,21 +695,21 @@ class Server {
                         if (n > 0) {
                             if (ng.session_mem_recv(c->session, buf,
                                                     (size_t)n) < 0) {
-                                destroy_conn(c.get(), true);
+                                destroy_conn(c.get());
                                 break;
                             }
                         } else if (n == 0) {
-                            destroy_conn(c.get(), true);
+                            destroy_conn(c.get());
                             break;
                         } else {
                             if (errno != EAGAIN && errno != EWOULDBLOCK)
-                                destroy_conn(c.get(), true);
+                                destroy_conn(c.get());
                             break;
                         }
                     }
                 }
                 if (!c->dead && !flush_conn(c.get()))
-                    destroy_conn(c.get(), true);
+                    destroy_conn(c.get());
             }
             conns_.erase(std::remove_if(conns_.begin(), conns_.end(),
                                         [](auto &c) { return c->dead; }),
@@ -1064,8 +735,6 @@ class Server {
     std::unordered_map<std::string, std::string> prestart_paths_;
     AllocState alloc_;
     bool pending_push_ = false;
-
-    friend struct Conn;
 };
 
 }  // namespace

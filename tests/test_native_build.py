@@ -26,6 +26,14 @@ def test_needs_build_any_newer_input(tmp_path):
     assert nb._needs_build(out, a, b)  # first input newer
 
 
+def test_pref_alloc_header_is_a_fastserver_build_input(monkeypatch):
+    checked = []
+    monkeypatch.setattr(
+        nb, "_needs_build", lambda out, *inputs: checked.extend(inputs))
+    nb.build_fastserver()  # _needs_build is falsy: nothing is compiled
+    assert os.path.join(nb.PKG_DIR, "pref_alloc.h") in checked
+
+
 @pytest.mark.skipif(shutil.which(nb.HIPCC) is None, reason="no hipcc")
 def test_build_sweeps_produces_both_binaries():
     outs = nb.build_sweeps()
