@@ -166,6 +166,12 @@ def deep_health_probe(
     mod = load_healthprobe(required=True)
     res = mod.run_probe(device=device, hbm_bytes=hbm_bytes)
     violations = []
+    if res.get("hbm_copy_ok") is False:
+        # the whole copy is compared with the fill pattern on the device
+        violations.append(
+            "hbm_copy: {} elements differ from the pattern, first at {}".format(
+                res.get("hbm_mismatches", "?"), res.get("hbm_first_bad", "?"))
+        )
     mfma = res.get("mfma_tflops")
     if mfma_floor_tflops > 0 and mfma is not None and mfma < mfma_floor_tflops:
         violations.append(

@@ -86,6 +86,7 @@ double bench(K kernel, const float4 *src, float4 *dst, size_t n, int blocks,
 
 static void sweep(size_t bytes) {
     size_t n = bytes / sizeof(float4);
+    if (n == 0) throw std::invalid_argument("bytes must be at least 16 (one float4)");
     DeviceBuffer<float4> src_buf(n), dst_buf(n);
     float4 *src = src_buf.get(), *dst = dst_buf.get();
     hipLaunchKernelGGL(fill_pattern_kernel, dim3(8192), dim3(256), 0, 0, src, n);
@@ -106,12 +107,27 @@ static void sweep(size_t bytes) {
         if (tu > best.gbps) best = {"nt_unroll4", tu};
     }
     {
-        // the probe's kernel on an exact-fit grid: every thread does its 4
-        // elements, no loop
-        int blocks = (int)(n / (256 * 4));
+        // the probe's kernel on the probe's grid, rounded up: at an n that is
+        // no multiple of 1024 the last threads take the tail path, and the
+        // GB/s counts only elements that were copied.  dst is poisoned first
+        // and then compared with the pattern, all of it.
+        int blocks = (int)hbm_copy_blocks(n, 256);
+        HIP_CHECK(hipMemset(dst, hbmpattern::kPoisonByte, n * sizeof(float4)));
         double o = bench(hbm_copy_kernel, src, dst, n, blocks, 256, iters);
         printf("oneshot blocks=%d nt_oneshot=%7.0f GB/s\n", blocks, o);
         if (o > best.gbps) best = {"nt_oneshot", o};
+
+        DeviceBuffer<unsigned long long> verdict(2);
+        unsigned long long h[2] = {0, ~0ull};
+        HIP_CHECK(hipMemcpy(verdict.get(), h, sizeof(h), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(verify_pattern_kernel, dim3(blocks), dim3(256), 0, 0,
+                           dst, n, verdict.get(), verdict.get() + 1);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpy(h, verdict.get(), sizeof(h), hipMemcpyDeviceToHost));
+        printf("oneshot copied %zu elements, %llu differ from the pattern\n", n, h[0]);
+        if (h[0])
+            throw std::runtime_error("oneshot copy is wrong, first at element " +
+                                     std::to_string(h[1]));
     }
     printf("BEST %s %.0f GB/s\n", best.name, best.gbps);
 }

@@ -8,7 +8,8 @@
 //      (v_mfma_f32_16x16x32_bf16 invariant checks, exact in bf16/f32);
 //   3. LDS write/read round-trips a full 128 KiB per CU;
 //   4. HBM sustains a float4 streaming copy at a reportable GB/s
-//      (grid sized >>256 workgroups to cover all 8 XCDs);
+//      (grid sized >>256 workgroups to cover all 8 XCDs), and every element
+//      of the copy equals a pattern that does not repeat (hbm_pattern.h);
 //   5. on request (cu_sweep), exact known-answer products of the bf16, f16,
 //      fp8, i8 and MX-fp8 matrix pipes on every SIMD of every CU, with the
 //      place each wave ran read from the hardware id registers.
@@ -21,6 +22,7 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <initializer_list>
 #include <cstring>
 #include <map>
 #include <string>
@@ -85,14 +87,18 @@ MfmaResult check_mfma() {
 // sweep (profiles/r01_bench_mi355x.md), whose 8-accumulator build had no
 // launch bounds, was capped at 128 VGPRs and spilled (152 TF/s).  Under
 // the kernel's launch bounds the compiler reports no spill for any width:
-// 40 / 72 / 136 VGPRs, 0 scratch, occupancy 8 / 7 / 3 waves per SIMD for
-// 2 / 4 / 8 accumulators; run the sweep again before changing the choice.
+// 42 / 74 / 138 VGPRs, 0 scratch, occupancy 8 / 6 / 3 waves per SIMD for
+// 2 / 4 / 8 accumulators (the store argument costs 2 VGPRs, and <4> a
+// seventh wave); run the sweep again before changing the choice.
+// mfma_peak_check runs this same instantiation with store = 1 and the tests
+// compare its accumulators with iters * (A @ B): the iters * 2 MFMAs per
+// wave that the formula below counts are the ones that ran.
 double measure_mfma_tflops(int cu_count) {
     DeviceBuffer<float> d(4096);
     const int iters = 8192, blocks = cu_count * 2;
     auto launch = [&](int n) {
         hipLaunchKernelGGL(mfma_peak_kernel<2>, dim3(blocks), dim3(512), 0, 0,
-                           d.get(), n);
+                           d.get(), n, 0);
     };
     float ms = timed_ms([&] { launch(64); }, [&] { launch(iters); });
     // FLOPs: blocks * 8 waves * iters * 2 MFMA * 2*32*32*16
@@ -105,35 +111,64 @@ struct LdsResult {
     int bytes_tested;
 };
 
-// 128 KiB dynamic LDS per workgroup (160 KiB/CU on gfx950), one per CU
-LdsResult check_lds(int cu_count) {
-    const int lds_bytes = 128 * 1024;
+// lds_probe_kernel on blocks workgroups of lds_bytes dynamic LDS each;
+// returns the raw error count.  corrupt_block = -1: nothing corrupted.
+uint32_t run_lds_probe(int blocks, int threads, int lds_bytes,
+                       int corrupt_block, int corrupt_word,
+                       uint32_t corrupt_mask) {
     DeviceBuffer<uint32_t> d_err(1);
     HIP_CHECK(hipMemset(d_err.get(), 0, sizeof(uint32_t)));
-    hipLaunchKernelGGL(lds_probe_kernel, dim3(cu_count), dim3(256), lds_bytes,
-                       0, d_err.get(), lds_bytes / 4);
+    hipLaunchKernelGGL(lds_probe_kernel, dim3(blocks), dim3(threads), lds_bytes,
+                       0, d_err.get(), lds_bytes / 4, corrupt_block,
+                       corrupt_word, corrupt_mask);
     HIP_CHECK(hipGetLastError());
     uint32_t h_err = 1;
     HIP_CHECK(hipMemcpy(&h_err, d_err.get(), sizeof(h_err),
                         hipMemcpyDeviceToHost));
-    return {h_err == 0, lds_bytes};
+    return h_err;
+}
+
+// 128 KiB dynamic LDS per workgroup (160 KiB/CU on gfx950), one per CU
+LdsResult check_lds(int cu_count) {
+    const int lds_bytes = 128 * 1024;
+    return {run_lds_probe(cu_count, 256, lds_bytes, -1, -1, 0) == 0, lds_bytes};
+}
+
+struct PatternResult {
+    unsigned long long mismatches;
+    long long first_bad;  // lowest differing index, -1 when there is none
+};
+
+// verify_pattern_kernel over all n elements of buf.
+PatternResult verify_pattern(const float4 *buf, size_t n) {
+    DeviceBuffer<unsigned long long> d(2);
+    unsigned long long h[2] = {0, ~0ull};
+    HIP_CHECK(hipMemcpy(d.get(), h, sizeof(h), hipMemcpyHostToDevice));
+    // the fill's grid: four elements per thread, grid-stride
+    hipLaunchKernelGGL(verify_pattern_kernel, dim3((unsigned)hbm_copy_blocks(n)),
+                       dim3(256), 0, 0, buf, n, d.get(), d.get() + 1);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpy(h, d.get(), sizeof(h), hipMemcpyDeviceToHost));
+    return {h[0], h[0] ? (long long)h[1] : -1};
 }
 
 struct HbmResult {
     double gbps;
     uint64_t bytes_tested;
     bool copy_ok;
+    PatternResult verdict;
 };
 
-// Streaming copy bandwidth (read+write) of n >= 1 float4s, then a spot
-// check of the copy against the fill pattern.
+// Streaming copy bandwidth (read+write) of n >= 1 float4s, then a check of
+// the WHOLE copy against the fill pattern.  dst is poisoned first, so an
+// element that no thread wrote cannot pass on what the allocation held.
 HbmResult check_hbm(size_t n) {
     DeviceBuffer<float4> src(n), dst(n);
+    HIP_CHECK(hipMemset(dst.get(), hbmpattern::kPoisonByte, n * sizeof(float4)));
     // exact-fit grid: one thread per 4 float4s (no loop), which was the
     // fastest measured formulation; still >>256 workgroups for all 8 XCDs
     const int threads = 256, iters = 5;
-    long want = (long)((n + threads * 4 - 1) / (threads * 4));
-    const int blocks = (int)(want < 1024 ? 1024 : want);
+    const int blocks = (int)hbm_copy_blocks(n, threads);
     auto copy = [&] {
         hipLaunchKernelGGL(hbm_copy_kernel, dim3(blocks), dim3(threads), 0, 0,
                            src.get(), dst.get(), n);
@@ -149,22 +184,9 @@ HbmResult check_hbm(size_t n) {
         });
     double gbps = (2.0 * n * sizeof(float4) * iters) / (ms * 1e6);
 
-    // min(16, n) elements at the head, the middle and the end of dst
-    const size_t m = std::min<size_t>(16, n);
-    bool copy_ok = true;
-    for (size_t first : {(size_t)0, std::min(n / 2, n - m), n - m}) {
-        float4 sample[16];
-        HIP_CHECK(hipMemcpy(sample, dst.get() + first, m * sizeof(float4),
-                            hipMemcpyDeviceToHost));
-        for (size_t k = 0; k < m; ++k) {
-            float v = (float)((first + k) & 0xFFFF);
-            const float4 &s = sample[k];
-            if (s.x != v || s.y != v + 0.25f || s.z != v + 0.5f ||
-                s.w != v + 0.75f)
-                copy_ok = false;
-        }
-    }
-    return {gbps, (uint64_t)(n * sizeof(float4)), copy_ok};
+    const PatternResult verdict = verify_pattern(dst.get(), n);
+    return {gbps, (uint64_t)(n * sizeof(float4)), verdict.mismatches == 0,
+            verdict};
 }
 
 py::dict run_probe(int device, size_t hbm_bytes) {
@@ -196,6 +218,8 @@ py::dict run_probe(int device, size_t hbm_bytes) {
     result["hbm_gbps"] = hbm.gbps;
     result["hbm_bytes_tested"] = hbm.bytes_tested;
     result["hbm_copy_ok"] = hbm.copy_ok;
+    result["hbm_mismatches"] = hbm.verdict.mismatches;
+    result["hbm_first_bad"] = hbm.verdict.first_bad;
     result["healthy"] = wave.ok && mfma.const_ok && mfma.sum_ok && lds.ok &&
                         hbm.copy_ok;
     return result;
@@ -215,6 +239,203 @@ py::dict mfma_probe_raw(int device) {
     out["pass1"] = pass[1];  // D = A_pattern @ ones, per-lane fragments
     out["pass2"] = pass[2];  // D = A_pattern @ B_pattern (asymmetric both)
     return out;
+}
+
+// ---------------- the default checks, one at a time, for the tests ----------------
+//
+// Each entry validates its arguments before any HIP call (ValueError), so
+// the rejections are testable without a GPU.
+
+void require_whole_waves(int threads) {
+    if (threads < 64 || threads > 1024 || threads % 64)
+        throw std::invalid_argument(
+            "threads must be a multiple of 64 in 64..1024");
+}
+
+constexpr long long kCopyCheckMaxN = 1ll << 32;      // 64 GiB per buffer
+constexpr long long kCopyCheckMaxGuard = 1ll << 20;  // float4s per band
+constexpr long long kCopyCheckMaxData = 1ll << 21;   // n for return_data
+
+// ONE hbm_copy_kernel launch of n float4s into the middle of a poisoned
+// guard + n + guard allocation (guard counts float4s), then the device
+// verifier over the n elements and a host check that both guard bands still
+// hold the poison.  blocks = 0 takes the production grid, hbm_copy_blocks.
+// corrupt damages dst between the copy and the verifier, from the host, with
+// hipMemcpy inside the allocation and no kernel:
+//   ("flip", index, component, bit)   flips one bit of one float
+//   ("alias", index, distance)        element index := element index + distance
+py::dict hbm_copy_check(int device, long long n, long long blocks, int threads,
+                        long long guard, py::object corrupt, bool return_data) {
+    if (n < 1 || n > kCopyCheckMaxN)
+        throw std::invalid_argument("n must be in 1..2^32");
+    require_whole_waves(threads);
+    if (blocks < 0 || blocks > INT32_MAX)
+        throw std::invalid_argument("blocks must be in 0..2^31-1 (0 = default)");
+    if (blocks == 0) blocks = (long long)hbm_copy_blocks((size_t)n, threads);
+    if (blocks > INT32_MAX)
+        throw std::invalid_argument("n needs more than 2^31-1 blocks");
+    if (4 * blocks * threads < n)
+        throw std::invalid_argument(
+            "hbm_copy_kernel needs 4 * blocks * threads >= n");
+    if (guard < 0 || guard > kCopyCheckMaxGuard)
+        throw std::invalid_argument("guard must be in 0..2^20 float4s");
+    if (return_data && n > kCopyCheckMaxData)
+        throw std::invalid_argument("return_data needs n <= 2^21");
+    enum { kNone, kFlip, kAlias } kind = kNone;
+    long long c_index = 0, c_component = 0, c_bit = 0, c_distance = 0;
+    if (!corrupt.is_none()) {
+        py::sequence seq = corrupt.cast<py::sequence>();
+        const std::string what =
+            py::len(seq) ? seq[0].cast<std::string>() : std::string();
+        if (what == "flip" && py::len(seq) == 4) {
+            kind = kFlip;
+            c_index = seq[1].cast<long long>();
+            c_component = seq[2].cast<long long>();
+            c_bit = seq[3].cast<long long>();
+            if (c_component < 0 || c_component > 3 || c_bit < 0 || c_bit > 31)
+                throw std::invalid_argument(
+                    "flip: component in 0..3, bit in 0..31");
+        } else if (what == "alias" && py::len(seq) == 3) {
+            kind = kAlias;
+            c_index = seq[1].cast<long long>();
+            c_distance = seq[2].cast<long long>();
+            if (c_index < 0 || c_index >= n || c_distance == 0 ||
+                c_distance <= -n || c_distance >= n ||
+                c_index + c_distance < 0 || c_index + c_distance >= n)
+                throw std::invalid_argument(
+                    "alias: index + distance must be another element of 0..n-1");
+        } else {
+            throw std::invalid_argument(
+                "corrupt must be ('flip', index, component, bit) or "
+                "('alias', index, distance)");
+        }
+        if (c_index < 0 || c_index >= n)
+            throw std::invalid_argument("corrupt: index must be in 0..n-1");
+    }
+
+    HIP_CHECK(hipSetDevice(device));
+    const size_t total = (size_t)(guard + n + guard);
+    DeviceBuffer<float4> src((size_t)n), dst(total);
+    float4 *out = dst.get() + guard;
+    HIP_CHECK(hipMemset(dst.get(), hbmpattern::kPoisonByte,
+                        total * sizeof(float4)));
+    hipLaunchKernelGGL(fill_pattern_kernel, dim3((unsigned)hbm_copy_blocks(n)),
+                       dim3(256), 0, 0, src.get(), (size_t)n);
+    HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(hbm_copy_kernel, dim3((unsigned)blocks), dim3(threads), 0,
+                       0, src.get(), out, (size_t)n);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+
+    if (kind == kFlip) {
+        uint32_t *word = reinterpret_cast<uint32_t *>(out + c_index) + c_component;
+        uint32_t w = 0;
+        HIP_CHECK(hipMemcpy(&w, word, sizeof(w), hipMemcpyDeviceToHost));
+        w ^= 1u << c_bit;
+        HIP_CHECK(hipMemcpy(word, &w, sizeof(w), hipMemcpyHostToDevice));
+    } else if (kind == kAlias) {
+        HIP_CHECK(hipMemcpy(out + c_index, out + c_index + c_distance,
+                            sizeof(float4), hipMemcpyDeviceToDevice));
+    }
+
+    const PatternResult verdict = verify_pattern(out, (size_t)n);
+
+    bool guard_ok = true;
+    std::vector<unsigned char> band((size_t)guard * sizeof(float4));
+    for (const float4 *from : {(const float4 *)dst.get(), (const float4 *)out + n}) {
+        if (band.empty()) break;
+        HIP_CHECK(hipMemcpy(band.data(), from, band.size(),
+                            hipMemcpyDeviceToHost));
+        for (unsigned char b : band)
+            if (b != hbmpattern::kPoisonByte) guard_ok = false;
+    }
+
+    const unsigned long long grid = (unsigned long long)blocks * threads;
+    const unsigned long long un = (unsigned long long)n;
+    // the kernel's condition i + 3 * stride < n, i = 0..stride-1
+    const unsigned long long wide =
+        un > 3 * grid ? std::min(un - 3 * grid, grid) : 0;
+
+    py::dict res;
+    res["mismatches"] = verdict.mismatches;
+    res["first_bad"] = verdict.first_bad;
+    res["guard_ok"] = guard_ok;
+    res["blocks"] = blocks;
+    res["threads"] = threads;
+    res["stride"] = grid;
+    res["wide_threads"] = wide;
+    res["tail_threads"] = grid - wide;
+    res["guard"] = guard;
+    res["poison_byte"] = hbmpattern::kPoisonByte;
+    if (return_data) {
+        std::vector<char> all(total * sizeof(float4));
+        HIP_CHECK(hipMemcpy(all.data(), dst.get(), all.size(),
+                            hipMemcpyDeviceToHost));
+        res["data"] = py::bytes(all.data(), all.size());  // guards included
+    }
+    return res;
+}
+
+// lds_probe_kernel at one shape; returns the raw error count.
+// corrupt = (block, word, mask) xors mask into that word of that block.
+long long lds_check(int device, long long lds_bytes, int blocks, int threads,
+                    py::object corrupt) {
+    if (lds_bytes <= 0 || lds_bytes % 4 || lds_bytes > (1ll << 30))
+        throw std::invalid_argument("lds_bytes must be a positive multiple of 4");
+    if (blocks < 1 || blocks > 65536)
+        throw std::invalid_argument("blocks must be in 1..65536");
+    require_whole_waves(threads);
+    long long c_block = -1, c_word = -1, c_mask = 0;
+    if (!corrupt.is_none()) {
+        py::sequence seq = corrupt.cast<py::sequence>();
+        if (py::len(seq) != 3)
+            throw std::invalid_argument("corrupt must be (block, word, mask)");
+        c_block = seq[0].cast<long long>();
+        c_word = seq[1].cast<long long>();
+        c_mask = seq[2].cast<long long>();
+        if (c_block < 0 || c_block >= blocks || c_word < 0 ||
+            c_word >= lds_bytes / 4 || c_mask < 1 || c_mask > 0xFFFFFFFFll)
+            throw std::invalid_argument(
+                "corrupt: block in 0..blocks-1, word in 0..lds_bytes/4-1, "
+                "mask in 1..2^32-1");
+    }
+
+    HIP_CHECK(hipSetDevice(device));
+    hipDeviceProp_t props;
+    HIP_CHECK(hipGetDeviceProperties(&props, device));
+    if ((size_t)lds_bytes > props.sharedMemPerBlock)
+        throw std::invalid_argument(
+            "lds_bytes is above this GPU's sharedMemPerBlock of " +
+            std::to_string(props.sharedMemPerBlock));
+    return run_lds_probe(blocks, threads, (int)lds_bytes, (int)c_block,
+                         (int)c_word, (uint32_t)c_mask);
+}
+
+size_t shared_mem_per_block(int device) {
+    hipDeviceProp_t props;
+    HIP_CHECK(hipGetDeviceProperties(&props, device));
+    return props.sharedMemPerBlock;
+}
+
+// The kernel that measure_mfma_tflops times, mfma_peak_kernel<2> at 512
+// threads, with store = 1: returns its accumulators as float32 bytes,
+// [blocks][8 waves][2 acc][16 regs][64 lanes].
+py::bytes mfma_peak_check(int device, int iters, int blocks) {
+    if (iters < 1 || iters > (1 << 20))
+        throw std::invalid_argument("iters must be in 1..2^20");
+    if (blocks < 1 || blocks > 4096)
+        throw std::invalid_argument("blocks must be in 1..4096");
+    HIP_CHECK(hipSetDevice(device));
+    std::vector<float> h((size_t)blocks * 8 * 2 * 16 * 64);
+    DeviceBuffer<float> d(h.size());
+    // NaN wherever no wave stores
+    HIP_CHECK(hipMemset(d.get(), 0xFF, h.size() * sizeof(float)));
+    hipLaunchKernelGGL(mfma_peak_kernel<2>, dim3(blocks), dim3(512), 0, 0,
+                       d.get(), iters, 1);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpy(h.data(), d.get(), h.size() * sizeof(float),
+                        hipMemcpyDeviceToHost));
+    return py::bytes((const char *)h.data(), h.size() * sizeof(float));
 }
 
 // ---------------- CU sweep ----------------
@@ -536,6 +757,16 @@ PYBIND11_MODULE(_healthprobe, m) {
     m.def("p2p_bandwidth", &p2p_bandwidth, py::arg("src") = 0,
           py::arg("dst") = 1, py::arg("bytes") = (size_t)1 << 30);
     m.def("mfma_probe_raw", &mfma_probe_raw, py::arg("device") = 0);
+    m.def("hbm_copy_check", &hbm_copy_check, py::arg("device") = 0,
+          py::arg("n") = 1, py::arg("blocks") = 0, py::arg("threads") = 256,
+          py::arg("guard") = 4096, py::arg("corrupt") = py::none(),
+          py::arg("return_data") = false);
+    m.def("lds_check", &lds_check, py::arg("device") = 0,
+          py::arg("lds_bytes") = 128 * 1024, py::arg("blocks") = 1,
+          py::arg("threads") = 256, py::arg("corrupt") = py::none());
+    m.def("shared_mem_per_block", &shared_mem_per_block, py::arg("device") = 0);
+    m.def("mfma_peak_check", &mfma_peak_check, py::arg("device") = 0,
+          py::arg("iters") = 8192, py::arg("blocks") = 2);
     m.def("cu_sweep", &cu_sweep, py::arg("device") = 0, py::arg("reps") = 0,
           py::arg("inject") = py::none());
     m.def("cu_sweep_reference", &cu_sweep_reference);

@@ -18,7 +18,7 @@ template <int NACC, bool ZERO = false>
 double bench(int blocks, int threads, int iters, float *d) {
     auto launch = [&](int n) {
         hipLaunchKernelGGL((mfma_peak_kernel<NACC, ZERO>), dim3(blocks),
-                           dim3(threads), 0, 0, d, n);
+                           dim3(threads), 0, 0, d, n, 0);
     };
     float ms = timed_ms([&] { launch(64); }, [&] { launch(iters); });
     double waves = (double)blocks * threads / 64;

@@ -7,6 +7,7 @@
 
 #include <cstdint>
 
+#include "hbm_pattern.h"
 #include "sweep_table.h"
 
 namespace {  // one translation unit per binary; keep the kernels internal
@@ -73,9 +74,14 @@ __global__ void mfma_probe_kernel(float *d_out /* [3][256] */) {
 // blocks/CU was fastest (2043 TF/s) — partner waves on each SIMD provide
 // the remaining issue cover (guide: §Two waves per SIMD).
 // ZERO feeds zero operands (the sweep's DVFS demonstration).
+// store != 0 (mfma_peak_check, the tests) writes the accumulators instead of
+// discarding them: wave w of block b puts acc[k][r] of its lane l at
+// out[(((b * waves + w) * NACC + k) * 16 + r) * 64 + l], waves = blockDim.x /
+// 64, so out holds blocks * waves * NACC * 16 * 64 floats.  The operands are
+// small integers: after iters rounds every acc[k] is exactly iters * (A @ B).
 template <int NACC, bool ZERO = false>
 __global__ void __launch_bounds__(512, 2)
-mfma_peak_kernel(float *out, int iters) {
+mfma_peak_kernel(float *out, int iters, int store) {
 #if defined(__gfx950__)
     int lane = threadIdx.x & 63;
     bf16x8 a, b;
@@ -90,6 +96,13 @@ mfma_peak_kernel(float *out, int iters) {
         for (int k = 0; k < NACC; ++k)
             acc[k] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc[k], 0, 0, 0);
     }
+    if (store) {
+        const size_t wave = (size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+        float *o = out + wave * NACC * 16 * 64 + lane;
+        for (int k = 0; k < NACC; ++k)
+            for (int r = 0; r < 16; ++r) o[(k * 16 + r) * 64] = acc[k][r];
+        return;
+    }
     float s = 0;
     for (int k = 0; k < NACC; ++k)
         for (int r = 0; r < 16; ++r) s += acc[k][r];
@@ -97,17 +110,28 @@ mfma_peak_kernel(float *out, int iters) {
 #else
     (void)out;
     (void)iters;
+    (void)store;
 #endif
 }
 
 // ---------------- LDS probe ----------------
 
-__global__ void lds_probe_kernel(uint32_t *err_count, int lds_words) {
+// Every thread of a block reads every word once, so one wrong word in one
+// block adds exactly blockDim.x to err_count.  corrupt_block / corrupt_word
+// (-1 = off) make thread 0 of that block xor corrupt_mask into that word
+// after the fill: a bad LDS cell simulated on healthy hardware (lds_check).
+__global__ void lds_probe_kernel(uint32_t *err_count, int lds_words,
+                                 int corrupt_block, int corrupt_word,
+                                 uint32_t corrupt_mask) {
     extern __shared__ uint32_t lds[];
     int tid = threadIdx.x;
     int nthreads = blockDim.x;
     for (int i = tid; i < lds_words; i += nthreads)
         lds[i] = (uint32_t)i * 2654435761u + blockIdx.x;
+    __syncthreads();
+    if (tid == 0 && (int)blockIdx.x == corrupt_block && corrupt_word >= 0 &&
+        corrupt_word < lds_words)
+        lds[corrupt_word] ^= corrupt_mask;
     __syncthreads();
     // read back with a stride so each thread checks other threads' writes
     uint32_t errors = 0;
@@ -124,6 +148,10 @@ __global__ void lds_probe_kernel(uint32_t *err_count, int lds_words) {
 // stream out of L1/L2, 4 independent loads per thread hide HBM latency —
 // fastest variant of the hbm_bench sweep, 6.22 TB/s on MI355X (99% of the
 // 6.29 TB/s float4-copy ceiling; profiles/r01_bench_mi355x.md).
+// PRECONDITION: 4 * gridDim.x * blockDim.x >= n.  A thread on the 4-wide path
+// never loops, so a smaller grid leaves elements from 4 * stride on uncopied;
+// hbm_copy_blocks() below is the grid of the probe and of hbm_bench;
+// hbm_copy_check refuses any other grid that is too small.
 __global__ void hbm_copy_kernel(const float4 *__restrict__ src4,
                                 float4 *__restrict__ dst4, size_t n) {
     const f32x4 *__restrict__ src = reinterpret_cast<const f32x4 *>(src4);
@@ -146,14 +174,47 @@ __global__ void hbm_copy_kernel(const float4 *__restrict__ src4,
     }
 }
 
-// buf[i] = (v, v+0.25, v+0.5, v+0.75) with v = float(i & 0xFFFF): exact in
-// fp32, so the host can check a copy bit for bit.
+// The grid of hbm_copy_kernel for n elements: one thread per 4 float4s,
+// rounded UP so that the kernel's precondition holds for every n, and never
+// fewer than 1024 blocks (>>256 workgroups for all 8 XCDs).
+constexpr size_t hbm_copy_blocks(size_t n, int threads = 256) {
+    const size_t per_block = (size_t)threads * 4;
+    const size_t want = (n + per_block - 1) / per_block;
+    return want < 1024 ? 1024 : want;
+}
+
+// buf[i] = hbmpattern::value(i): exact in fp32 and different for every
+// i < 2^48 (hbm_pattern.h), so a copy can be checked bit for bit and a
+// displaced element cannot pass for the right one.
 __global__ void fill_pattern_kernel(float4 *buf, size_t n) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     size_t stride = (size_t)gridDim.x * blockDim.x;
     for (; i < n; i += stride) {
-        float v = (float)(i & 0xFFFF);
-        buf[i] = make_float4(v, v + 0.25f, v + 0.5f, v + 0.75f);
+        const hbmpattern::Value v = hbmpattern::value(i);
+        buf[i] = make_float4(v.x, v.y, v.z, v.w);
+    }
+}
+
+// Compares all four components of all n elements of buf with the pattern,
+// bit for bit.  The host sets *mismatches = 0 and *first_bad = ~0 before the
+// launch; afterwards they hold the number of differing elements and the
+// lowest differing index.
+__global__ void verify_pattern_kernel(const float4 *__restrict__ buf, size_t n,
+                                      unsigned long long *mismatches,
+                                      unsigned long long *first_bad) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    size_t stride = (size_t)gridDim.x * blockDim.x;
+    unsigned long long bad = 0, first = ~0ull;
+    for (; i < n; i += stride) {
+        const float4 v = buf[i];
+        if (!hbmpattern::matches(i, v.x, v.y, v.z, v.w)) {
+            if (!bad) first = i;  // i only grows
+            ++bad;
+        }
+    }
+    if (bad) {
+        atomicAdd(mismatches, bad);
+        atomicMin(first_bad, first);
     }
 }
 
