@@ -110,14 +110,24 @@ bool for_each_field(const uint8_t *p, const uint8_t *end, F cb) {
 
 // ---------------- gRPC framing ----------------
 
+constexpr size_t kGrpcPrefix = 5;  // compressed flag + big-endian length
+
 std::string grpc_frame(const std::string &msg) {
     std::string out;
-    out.reserve(msg.size() + 5);
+    out.reserve(msg.size() + kGrpcPrefix);
     out.push_back('\0');
     uint32_t n = htonl((uint32_t)msg.size());
     out.append((const char *)&n, 4);
     out += msg;
     return out;
+}
+
+// A unary response is assembled behind kGrpcPrefix placeholder bytes and
+// framed in place, so the message is never copied into its frame.
+void grpc_frame_in_place(std::string &framed) {
+    framed[0] = '\0';
+    uint32_t n = htonl((uint32_t)(framed.size() - kGrpcPrefix));
+    memcpy(&framed[1], &n, 4);
 }
 
 // ---------------- server ----------------
@@ -143,7 +153,11 @@ struct Conn {
     int fd = -1;
     nghttp2_session *session = nullptr;
     std::map<int32_t, std::unique_ptr<Stream>> streams;
-    std::string wbuf;  // pending bytes the socket couldn't take yet
+    // Outgoing bytes: what the session had ready, gathered so that one
+    // write() sends it; [woff, size) is what the socket has not taken yet.
+    std::string wbuf;
+    size_t woff = 0;
+    bool want_out() const { return woff < wbuf.size(); }
     Server *srv = nullptr;
     bool dead = false;
 };
@@ -199,6 +213,11 @@ class Server {
         // Prometheus-style average handler latency via rate()/rate()
         d["allocate_handler_ns_total"] = (uint64_t)allocate_ns_.load();
         d["preferred_handler_ns_total"] = (uint64_t)preferred_ns_.load();
+        // transport: write()/read() calls on kubelet connections, and how
+        // often the socket took less than it was offered (back-pressure)
+        d["socket_writes_total"] = (uint64_t)n_writes_.load();
+        d["socket_reads_total"] = (uint64_t)n_reads_.load();
+        d["socket_write_would_block_total"] = (uint64_t)n_would_block_.load();
         return d;
     }
 
@@ -360,7 +379,8 @@ class Server {
         // INTERNAL(13).  Treating either as an empty request would turn
         // garbage into a bogus success (e.g. an Allocate response with
         // only /dev/kfd).
-        std::string msg;
+        const uint8_t *msg = nullptr;
+        size_t msg_len = 0;
         if (!st->req_body.empty()) {
             if (st->req_body.size() < 5)  // INTERNAL: truncated frame prefix
                 return submit_error(conn, stream_id, st, "13",
@@ -375,26 +395,27 @@ class Server {
             if (st->req_body.size() < (size_t)5 + len)  // INTERNAL
                 return submit_error(conn, stream_id, st, "13",
                                     "malformed grpc frame: truncated body");
-            msg = st->req_body.substr(5, len);
+            msg = (const uint8_t *)st->req_body.data() + 5;
+            msg_len = len;
         }
 
         const std::string &p = st->path;
-        std::string resp;
+        std::string resp(kGrpcPrefix, '\0');  // framed in submit_unary
         if (p == "/v1beta1.DevicePlugin/GetDevicePluginOptions") {
             n_options_.fetch_add(1, std::memory_order_relaxed);
             std::lock_guard<std::mutex> g(mu_);
-            resp = options_;
+            resp += options_;
         } else if (p == "/v1beta1.DevicePlugin/PreStartContainer") {
             n_prestart_.fetch_add(1, std::memory_order_relaxed);
             std::string bad;
-            if (!handle_prestart(msg, bad))  // FAILED_PRECONDITION
+            if (!handle_prestart(msg, msg_len, bad))  // FAILED_PRECONDITION
                 return submit_error(
                     conn, stream_id, st, "9",
                     "device " + bad + " failed the pre-start probe");
         } else if (p == "/v1beta1.DevicePlugin/Allocate") {
             n_allocate_.fetch_add(1, std::memory_order_relaxed);
             auto t0 = std::chrono::steady_clock::now();
-            resp = handle_allocate(msg);
+            handle_allocate(msg, msg_len, resp);
             allocate_ns_.fetch_add(
                 (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(
                     std::chrono::steady_clock::now() - t0).count(),
@@ -403,7 +424,7 @@ class Server {
             n_preferred_.fetch_add(1, std::memory_order_relaxed);
             auto t0 = std::chrono::steady_clock::now();
             std::string err;
-            bool ok = handle_preferred(msg, resp, err);
+            bool ok = handle_preferred(msg, msg_len, resp, err);
             preferred_ns_.fetch_add(
                 (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(
                     std::chrono::steady_clock::now() - t0).count(),
@@ -424,7 +445,7 @@ class Server {
             n_unknown_.fetch_add(1, std::memory_order_relaxed);
             return submit_error(conn, stream_id, st, "12", "");  // UNIMPLEMENTED
         }
-        submit_unary(conn, stream_id, st, resp, true);
+        submit_unary(conn, stream_id, st, std::move(resp));
     }
 
     // trailers-only style failure: no message body, status in the trailer
@@ -432,7 +453,7 @@ class Server {
                       const char *status, const std::string &message) {
         st->grpc_status = status;
         st->grpc_message = message;
-        submit_unary(conn, stream_id, st, "", false);
+        submit_unary(conn, stream_id, st, std::string());
     }
 
     void submit_headers_common(Conn *conn, int32_t stream_id, Stream *st) {
@@ -451,18 +472,21 @@ class Server {
         ng.submit_response(conn->session, stream_id, hdrs, 2, &prov);
     }
 
+    // `framed` is empty (no body) or kGrpcPrefix placeholder bytes followed
+    // by the message
     void submit_unary(Conn *conn, int32_t stream_id, Stream *st,
-                      const std::string &msg, bool with_body) {
+                      std::string &&framed) {
+        if (!framed.empty()) grpc_frame_in_place(framed);
         {
             std::lock_guard<std::mutex> g(mu_);
-            st->out = with_body ? grpc_frame(msg) : std::string();
+            st->out = std::move(framed);
             st->out_off = 0;
         }
         submit_headers_common(conn, stream_id, st);
     }
 
     // true = every requested device opens; on failure `bad` names it
-    bool handle_prestart(const std::string &msg, std::string &bad) {
+    bool handle_prestart(const uint8_t *p, size_t msg_len, std::string &bad) {
         std::unordered_map<std::string, std::string> paths;
         {
             std::lock_guard<std::mutex> g(mu_);
@@ -470,10 +494,9 @@ class Server {
             paths = prestart_paths_;
         }
         bool ok = true;
-        const uint8_t *p = (const uint8_t *)msg.data();
-        for_each_field(p, p + msg.size(), [&](int field, int wt,
-                                              const uint8_t *data,
-                                              uint64_t len) {
+        for_each_field(p, p + msg_len, [&](int field, int wt,
+                                           const uint8_t *data,
+                                           uint64_t len) {
             if (!ok || field != 1 || wt != 2) return;
             std::string id((const char *)data, len);
             auto it = paths.find(id);
@@ -489,16 +512,16 @@ class Server {
         return ok;
     }
 
-    std::string handle_allocate(const std::string &msg) {
+    // appends the AllocateResponse to resp
+    void handle_allocate(const uint8_t *p, size_t msg_len, std::string &resp) {
         std::lock_guard<std::mutex> g(mu_);
-        std::string resp;
-        const uint8_t *p = (const uint8_t *)msg.data();
-        for_each_field(p, p + msg.size(), [&](int field, int wt,
-                                              const uint8_t *data,
-                                              uint64_t len) {
+        std::string &car = car_;
+        for_each_field(p, p + msg_len, [&](int field, int wt,
+                                           const uint8_t *data,
+                                           uint64_t len) {
             if (field != 1 || wt != 2) return;
             // one ContainerAllocateRequest
-            std::string car = kfd_spec_;
+            car = kfd_spec_;
             for_each_field(data, data + len, [&](int f2, int wt2,
                                                  const uint8_t *d2,
                                                  uint64_t l2) {
@@ -509,19 +532,26 @@ class Server {
             });
             put_len_delim(resp, 1, car);
         });
-        return resp;
     }
 
-    bool handle_preferred(const std::string &msg, std::string &resp,
+    // appends the PreferredAllocationResponse to resp; the id lists, the
+    // response fragment and the search's scratch are members, reused from
+    // request to request (only this thread runs handlers, under mu_)
+    bool handle_preferred(const uint8_t *p, size_t msg_len, std::string &resp,
                           std::string &err) {
         std::lock_guard<std::mutex> g(mu_);
         bool ok = true;
-        const uint8_t *p = (const uint8_t *)msg.data();
-        for_each_field(p, p + msg.size(), [&](int field, int wt,
-                                              const uint8_t *data,
-                                              uint64_t len) {
+        std::vector<std::string> &available = pref_available_,
+                                 &required = pref_required_,
+                                 &chosen = pref_chosen_;
+        std::string &car = car_;
+        for_each_field(p, p + msg_len, [&](int field, int wt,
+                                           const uint8_t *data,
+                                           uint64_t len) {
             if (!ok || field != 1 || wt != 2) return;
-            std::vector<std::string> available, required;
+            available.clear();
+            required.clear();
+            chosen.clear();
             int size = 0;
             for_each_field(data, data + len, [&](int f2, int wt2,
                                                  const uint8_t *d2,
@@ -533,13 +563,12 @@ class Server {
                 else if (f2 == 3 && wt2 == 0)
                     size = (int)l2;
             });
-            std::vector<std::string> chosen;
-            if (!preferred_alloc(alloc_, available, required, size, chosen,
-                                 err)) {
+            if (!preferred_alloc(alloc_, scratch_, available, required, size,
+                                 chosen, err)) {
                 ok = false;
                 return;
             }
-            std::string car;
+            car.clear();
             for (auto &id : chosen) put_len_delim(car, 1, id);
             put_len_delim(resp, 1, car);
         });
@@ -597,38 +626,55 @@ class Server {
         c->dead = true;
     }
 
-    // returns false when the connection died
+    // How much is gathered before a write: about one read buffer.  A
+    // large ListAndWatch response or a burst of pipelined responses goes
+    // out in pieces of this size instead of growing the buffer.
+    static constexpr size_t kGatherLimit = 65536;
+
+    // Sends what the session has ready: everything session_mem_send()
+    // hands back (one frame per call) is gathered into the connection's
+    // buffer and goes out with one write(), so a unary response (HEADERS,
+    // DATA, trailer HEADERS) is one syscall.  When the socket takes less
+    // than it was offered the unsent tail stays, in order, behind an
+    // offset, and POLLOUT drives the rest.  Returns false when the
+    // connection died.
     bool flush_conn(Conn *c) {
         auto &ng = NgHttp2::get();
-        // drain pending wbuf first
-        while (!c->wbuf.empty()) {
-            ssize_t n = ::write(c->fd, c->wbuf.data(), c->wbuf.size());
+        for (;;) {
+            if (!c->want_out()) {
+                c->wbuf.clear();
+                c->woff = 0;
+            } else if (c->woff >= kGatherLimit) {
+                // drop the sent prefix once it outweighs the tail, so a
+                // long back-pressured stream does not keep what it sent
+                c->wbuf.erase(0, c->woff);
+                c->woff = 0;
+            }
+            while (c->wbuf.size() - c->woff < kGatherLimit) {
+                const uint8_t *data = nullptr;
+                ssize_t len = ng.session_mem_send(c->session, &data);
+                if (len < 0) return false;
+                if (len == 0) break;
+                c->wbuf.append((const char *)data, (size_t)len);
+            }
+            if (!c->want_out()) return true;
+            size_t want = c->wbuf.size() - c->woff;
+            ssize_t n = ::write(c->fd, c->wbuf.data() + c->woff, want);
+            n_writes_.fetch_add(1, std::memory_order_relaxed);
             if (n < 0) {
-                if (errno == EAGAIN || errno == EWOULDBLOCK) return true;
+                if (errno == EINTR) continue;
+                if (errno == EAGAIN || errno == EWOULDBLOCK) {
+                    n_would_block_.fetch_add(1, std::memory_order_relaxed);
+                    return true;
+                }
                 return false;
             }
-            c->wbuf.erase(0, (size_t)n);
-        }
-        for (;;) {
-            const uint8_t *data = nullptr;
-            ssize_t len = ng.session_mem_send(c->session, &data);
-            if (len < 0) return false;
-            if (len == 0) break;
-            ssize_t off = 0;
-            while (off < len) {
-                ssize_t n = ::write(c->fd, data + off, (size_t)(len - off));
-                if (n < 0) {
-                    if (errno == EAGAIN || errno == EWOULDBLOCK) {
-                        c->wbuf.assign((const char *)data + off,
-                                       (size_t)(len - off));
-                        return true;
-                    }
-                    return false;
-                }
-                off += n;
+            c->woff += (size_t)n;
+            if ((size_t)n < want) {  // the socket is full: wait for POLLOUT
+                n_would_block_.fetch_add(1, std::memory_order_relaxed);
+                return true;
             }
         }
-        return true;
     }
 
     void run_loop() {
@@ -641,7 +687,7 @@ class Server {
             pfds.push_back({wake_pipe_[0], POLLIN, 0});
             for (auto &c : conns_) {
                 short ev = POLLIN;
-                if (!c->wbuf.empty() || ng.session_want_write(c->session))
+                if (c->want_out() || ng.session_want_write(c->session))
                     ev |= POLLOUT;
                 pfds.push_back({c->fd, ev, 0});
             }
@@ -690,14 +736,20 @@ class Server {
                     continue;
                 }
                 if (rev & POLLIN) {
+                    // poll is level-triggered: after a read that did not
+                    // fill the buffer, whatever arrives later is reported
+                    // by the next poll, so there is no read just to see
+                    // EAGAIN
                     for (;;) {
                         ssize_t n = ::read(c->fd, buf, sizeof(buf));
+                        n_reads_.fetch_add(1, std::memory_order_relaxed);
                         if (n > 0) {
                             if (ng.session_mem_recv(c->session, buf,
                                                     (size_t)n) < 0) {
                                 destroy_conn(c.get());
                                 break;
                             }
+                            if ((size_t)n < sizeof(buf)) break;
                         } else if (n == 0) {
                             destroy_conn(c.get());
                             break;
@@ -727,13 +779,17 @@ class Server {
     std::atomic<uint64_t> allocate_ns_{0}, preferred_ns_{0};
     std::atomic<uint64_t> n_allocate_{0}, n_preferred_{0}, n_listwatch_{0},
         n_options_{0}, n_prestart_{0}, n_unknown_{0}, n_pushes_{0},
-        n_conns_{0};
+        n_conns_{0}, n_writes_{0}, n_reads_{0}, n_would_block_{0};
 
     std::mutex mu_;
     std::string options_, kfd_spec_, list_bytes_;
     std::unordered_map<std::string, std::string> dev_specs_;
     std::unordered_map<std::string, std::string> prestart_paths_;
     AllocState alloc_;
+    // request-path buffers, reused; touched only under mu_
+    prefalloc::Scratch scratch_;
+    std::vector<std::string> pref_available_, pref_required_, pref_chosen_;
+    std::string car_;
     bool pending_push_ = false;
 };
 

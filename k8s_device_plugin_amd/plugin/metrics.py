@@ -25,6 +25,11 @@ _COUNTER_HELP = {
     "unknown_method_total": "RPCs to unknown methods",
     "list_pushes_total": "device-list updates pushed to streams",
     "connections_total": "kubelet connections accepted",
+    "socket_writes_total": "write() calls on kubelet connections",
+    "socket_reads_total": "read() calls on kubelet connections",
+    "socket_write_would_block_total": (
+        "writes the socket took none or only part of (back-pressure)"
+    ),
 }
 
 

@@ -122,6 +122,9 @@ class H2Conn:
         self._buf = b""
         self._hdr_frag: Dict[int, bytes] = {}
         self._hdr_flags: Dict[int, int] = {}
+        # False: received DATA is not answered with WINDOW_UPDATEs (for a
+        # test that opened the windows wide and counts what the peer reads)
+        self.auto_window_update = True
         from ..native import _load
 
         self._dec = _load("_h2tool").HpackDecoder()
@@ -267,7 +270,7 @@ class H2Conn:
             if flags & FLAG_END_STREAM:
                 st.ended = True
             # naive flow control: restore both windows
-            if payload:
+            if payload and self.auto_window_update:
                 self.window_update(len(payload), 0)
                 if not st.ended:
                     self.window_update(len(payload), sid)
@@ -278,6 +281,21 @@ class H2Conn:
         elif ftype == GOAWAY:
             last, code = struct.unpack("!II", payload[:8])
             self.goaway = (last, code, payload[8:])
+
+    def _feed(self, chunk: bytes) -> None:
+        self._buf += chunk
+        pos = 0
+        while len(self._buf) - pos >= 9:
+            ln = struct.unpack("!I", b"\x00" + self._buf[pos:pos + 3])[0]
+            if len(self._buf) - pos < 9 + ln:
+                break
+            ftype, flags = self._buf[pos + 3], self._buf[pos + 4]
+            sid = struct.unpack(
+                "!I", self._buf[pos + 5:pos + 9])[0] & 0x7FFFFFFF
+            payload = self._buf[pos + 9:pos + 9 + ln]
+            pos += 9 + ln
+            self._on_frame(ftype, flags, sid, payload)
+        self._buf = self._buf[pos:]
 
     def pump(self, timeout: float = 0.5) -> bool:
         """Read whatever arrives within `timeout`; False on clean EOF."""
@@ -295,16 +313,7 @@ class H2Conn:
             if not chunk:
                 alive = False
                 break
-            self._buf += chunk
-            while len(self._buf) >= 9:
-                ln = struct.unpack("!I", b"\x00" + self._buf[:3])[0]
-                if len(self._buf) < 9 + ln:
-                    break
-                ftype, flags = self._buf[3], self._buf[4]
-                sid = struct.unpack("!I", self._buf[5:9])[0] & 0x7FFFFFFF
-                payload = self._buf[9:9 + ln]
-                self._buf = self._buf[9 + ln:]
-                self._on_frame(ftype, flags, sid, payload)
+            self._feed(chunk)
             # return early once quiet? keep simple: read until timeout
             self.sock.settimeout(
                 max(0.05, deadline - time.monotonic())
@@ -319,6 +328,25 @@ class H2Conn:
             if not self.pump(0.2):
                 return cond()
         return cond()
+
+    def wait_now(self, cond, timeout: float = 5.0) -> bool:
+        """Like wait(), but returns the moment cond() holds instead of
+        reading on to the end of a time slice: for tests that await many
+        responses one after another."""
+        deadline = time.monotonic() + timeout
+        while not cond():
+            left = deadline - time.monotonic()
+            if left <= 0:
+                return False
+            self.sock.settimeout(left)
+            try:
+                chunk = self.sock.recv(65536)
+            except OSError:  # socket.timeout included
+                return cond()
+            if not chunk:
+                return cond()
+            self._feed(chunk)
+        return True
 
     def close(self) -> None:
         try:
