@@ -359,6 +359,98 @@ def partition_main(argv=None) -> int:
     return 0
 
 
+def _byte_count(text: str):
+    return "all" if text.strip().lower() == "all" else int(text, 0)
+
+
+def scrub_main(argv=None) -> int:
+    """Operator tool: march test of the free VRAM of one or every HIP device.
+
+    Run it on a drained node: it takes all free VRAM but --reserve-bytes.
+    Exit 0 healthy, 1 unhealthy, 2 no GPU, no extension or a scrub that
+    could not run.
+    """
+    ap = argparse.ArgumentParser(
+        prog="amd-hbm-scrub",
+        description="In-place march test of GPU memory (HBM scrub)",
+    )
+    ap.add_argument("--device", default="0",
+                    help="HIP ordinal, or all: every ordinal one after the "
+                         "other (CPX mode: every partition)")
+    ap.add_argument("--bytes", default="all", type=_byte_count,
+                    help="bytes to test, or all (default): free VRAM less "
+                         "--reserve-bytes")
+    ap.add_argument("--reserve-bytes", type=lambda s: int(s, 0),
+                    default=None, help="VRAM left alone with --bytes all "
+                                       "(default 2 GiB)")
+    ap.add_argument("--patterns", default=None,
+                    help="comma-separated subset of address,solid,checker,"
+                         "random (default: all four)")
+    ap.add_argument("--json", action="store_true",
+                    help="print the full result per device as JSON")
+    ap.add_argument("--sysroot", default="/", help="sysfs root override (tests)")
+    args = ap.parse_args(argv)
+
+    import json
+
+    from . import native
+
+    try:
+        mod = native.load_healthprobe(required=True)
+    except native.NativeExtensionMissing as e:
+        print(f"error: {e}", file=sys.stderr)
+        return 2
+    count = mod.device_count()
+    if count < 1:
+        print("error: no HIP device visible", file=sys.stderr)
+        return 2
+    if args.device.strip().lower() == "all":
+        devices = list(range(count))
+    else:
+        try:
+            devices = [int(args.device)]
+        except ValueError:
+            ap.error("--device takes an ordinal or all")
+        if not 0 <= devices[0] < count:
+            print(f"error: device {devices[0]} not in 0..{count - 1}",
+                  file=sys.stderr)
+            return 2
+    kwargs = {}
+    if args.reserve_bytes is not None:
+        kwargs["reserve_bytes"] = args.reserve_bytes
+    if args.patterns:
+        kwargs["patterns"] = [p.strip() for p in args.patterns.split(",")]
+
+    # A scrub that could not run (nothing free to test, no slab obtained, a
+    # bad argument) is not a sick GPU: that device reports its error, the
+    # others still run, and the exit code is 2 unless some GPU is unhealthy.
+    healthy = True
+    failed = False
+    results = {}
+    for device in devices:
+        try:
+            res = native.hbm_scrub(device=device, bytes=args.bytes,
+                                   sysroot=args.sysroot, mod=mod, **kwargs)
+        except (ValueError, RuntimeError) as e:
+            print(f"error: device {device}: {e}", file=sys.stderr)
+            results[device] = {"error": str(e), "healthy": None}
+            failed = True
+            continue
+        results[device] = res
+        healthy = healthy and res["healthy"]
+        if not args.json:
+            print("device {}: {} bytes in {:.0f} ms, {}".format(
+                device, res["bytes_tested"], res["scrub_ms"],
+                "healthy" if res["healthy"] else "UNHEALTHY"))
+            for line in res["violations"] + res["warnings"]:
+                print(f"  {line}")
+    if args.json:
+        print(json.dumps({str(d): r for d, r in results.items()}, indent=2))
+    if not healthy:
+        return 1
+    return 2 if failed else 0
+
+
 if __name__ == "__main__":
     prog = os.path.basename(sys.argv[0])
     if "labeller" in prog or (len(sys.argv) > 1 and sys.argv[1] == "labeller"):

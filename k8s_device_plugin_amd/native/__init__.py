@@ -139,12 +139,131 @@ def run_cu_sweep(device: int = 0, mod=None) -> dict:
     return mod.cu_sweep(device=device, inject=_sweep_inject_from_env())
 
 
+HBM_SCRUB_ENV = "AMDXDP_HBM_SCRUB_BYTES"
+HBM_SCRUB_DEFAULT_RESERVE = 2 << 30
+# below this share of the card's VRAM a scrub of "all" says that it was partial
+HBM_SCRUB_FULL_SHARE = 0.9
+
+
+def hbm_scrub_bytes_from_env(hbm_scrub_bytes=None):
+    """An explicit argument wins; None reads AMDXDP_HBM_SCRUB_BYTES.  Returns
+    None (off: unset, empty or 0), "all" or a positive int."""
+    spec = hbm_scrub_bytes
+    if spec is None:
+        spec = os.environ.get(HBM_SCRUB_ENV, "")
+    if isinstance(spec, str):
+        spec = spec.strip().lower()
+        if spec in ("", "0"):
+            return None
+        if spec == "all":
+            return "all"
+        try:
+            spec = int(spec, 0)
+        except ValueError:
+            raise ValueError(
+                f"{HBM_SCRUB_ENV}={spec!r}: expected all or a byte count"
+            ) from None
+    spec = int(spec)
+    if spec < 0:
+        raise ValueError("hbm_scrub_bytes must not be negative")
+    return spec or None
+
+
+def read_ecc_counts(bdf: str, sysroot: str = "/"):
+    """{"ue": n, "ce": n} from <sysroot>/sys/bus/pci/devices/<bdf>/ras/
+    umc_err_count (lines of `key: integer`, other keys ignored), or None when
+    the file cannot be read or does not hold both."""
+    path = os.path.join(sysroot, "sys/bus/pci/devices", bdf, "ras",
+                        "umc_err_count")
+    counts = {}
+    try:
+        with open(path) as f:
+            for line in f:
+                key, sep, value = line.partition(":")
+                if sep and key.strip() in ("ue", "ce"):
+                    counts[key.strip()] = int(value.strip(), 0)
+    except (OSError, ValueError):
+        return None
+    return counts if len(counts) == 2 else None
+
+
+def hbm_scrub_violations(scrub: dict) -> list:
+    """One line per bad 2 MiB-aligned range, one for an overwritten guard."""
+    lines = []
+    for r in scrub.get("bad_ranges", []):
+        line = "hbm_scrub: {} bad elements in bytes {:#x}-{:#x}".format(
+            r["mismatches"], r["start"], r["end"])
+        first = r.get("first")
+        if first:
+            line += " (pattern {} step {}, bits {:#010x} in word {})".format(
+                first["pattern"], first["step"],
+                first["got"] ^ first["expected"], first["word"])
+        lines.append(line)
+    if scrub.get("guard_ok") is False:
+        lines.append("hbm_scrub: guard band overwritten")
+    return lines
+
+
+def hbm_scrub(device: int = 0, bytes=None,
+              reserve_bytes: int = HBM_SCRUB_DEFAULT_RESERVE,
+              sysroot: str = "/", mod=None, patterns=None) -> dict:
+    """In-place march test of device memory (native/hbm_march.h).
+
+    bytes=None or "all" takes the free VRAM less reserve_bytes; run it on a
+    drained node.  Adds `healthy`, `violations`, `warnings` and `ecc` (the
+    umc_err_count counters before and after, None when unreadable) to the
+    module's result.  A scrub of "all" that reached under 90 % of the card
+    only warns: a scrub that could not look is not a sick GPU.
+    """
+    if mod is None:
+        mod = load_healthprobe(required=True)
+    whole = bytes is None or bytes == "all"
+    if whole:
+        free, _total = mod.mem_info(device)
+        bytes = (int(free) - int(reserve_bytes)) // 16 * 16
+        if bytes < 16:
+            raise ValueError(
+                f"hbm_scrub: {free} bytes free, reserve_bytes={reserve_bytes}"
+                " leaves nothing to test")
+    bdf = None
+    try:
+        bdf = mod.pci_bus_ids()[device].lower()
+    except Exception:
+        pass
+    ecc_before = read_ecc_counts(bdf, sysroot) if bdf else None
+    kwargs = {} if patterns is None else {"patterns": list(patterns)}
+    res = mod.hbm_scrub(device=device, bytes=int(bytes), **kwargs)
+    ecc_after = read_ecc_counts(bdf, sysroot) if bdf else None
+
+    violations = hbm_scrub_violations(res)
+    warnings = []
+    if whole and res["bytes_tested"] < HBM_SCRUB_FULL_SHARE * res["vram_bytes"]:
+        warnings.append("hbm_scrub_partial: tested {} of {} bytes".format(
+            res["bytes_tested"], res["vram_bytes"]))
+    res["ecc"] = None
+    if ecc_before is not None and ecc_after is not None:
+        res["ecc"] = {"before": ecc_before, "after": ecc_after}
+        ue = ecc_after["ue"] - ecc_before["ue"]
+        ce = ecc_after["ce"] - ecc_before["ce"]
+        if ue > 0:
+            violations.append(
+                f"hbm_scrub: {ue} uncorrectable ECC errors during the scrub")
+        if ce > 0:
+            warnings.append(
+                f"hbm_scrub_ecc: {ce} corrected ECC errors during the scrub")
+    res["violations"] = violations
+    res["warnings"] = warnings
+    res["healthy"] = not violations
+    return res
+
+
 def deep_health_probe(
     device: int = 0,
     hbm_bytes: int = 1 << 30,
     mfma_floor_tflops: Optional[float] = None,
     hbm_floor_gbps: Optional[float] = None,
     cu_sweep: Optional[bool] = None,
+    hbm_scrub_bytes=None,
 ) -> dict:
     """Run the on-GPU MFMA/LDS/HBM probe and apply performance floors.
 
@@ -156,6 +275,10 @@ def deep_health_probe(
     MFMA sweep of every CU and SIMD under `cu_sweep`: a bad SIMD makes the
     GPU unhealthy, with one violation line each; a sweep that could not reach
     every SIMD but found nothing bad only sets `warnings`.
+
+    hbm_scrub_bytes (None = env AMDXDP_HBM_SCRUB_BYTES, default off; "all" or
+    a byte count) adds the march test of that much VRAM under `hbm_scrub`;
+    its violations and warnings join `floor_violations` and `warnings`.
     """
     if mfma_floor_tflops is None:
         mfma_floor_tflops = _floor_from_env(MFMA_FLOOR_ENV,
@@ -194,6 +317,13 @@ def deep_health_probe(
                     sweep.get("cus_covered"), sweep.get("cu_count"),
                     sweep.get("simds_covered"))
             ]
+    scrub_bytes = hbm_scrub_bytes_from_env(hbm_scrub_bytes)
+    if scrub_bytes is not None:
+        scrub = hbm_scrub(device, scrub_bytes, mod=mod)
+        res["hbm_scrub"] = scrub
+        violations.extend(scrub["violations"])
+        if scrub["warnings"]:
+            res.setdefault("warnings", []).extend(scrub["warnings"])
     res["floor_violations"] = violations
     if violations:
         res["healthy"] = False

@@ -12,7 +12,10 @@
 //      of the copy equals a pattern that does not repeat (hbm_pattern.h);
 //   5. on request (cu_sweep), exact known-answer products of the bf16, f16,
 //      fp8, i8 and MX-fp8 matrix pipes on every SIMD of every CU, with the
-//      place each wave ran read from the hardware id registers.
+//      place each wave ran read from the hardware id registers;
+//   6. on request (hbm_scrub), in-place march passes over all free VRAM:
+//      fused read-verify-write at streaming rate, four data patterns and
+//      their complements (hbm_march.h).
 //
 // Used by the plugin's optional deep health check, __graft_entry__.smoke(),
 // and the gpu-marked tests.  The kernels live in probe_kernels.h (shared
@@ -21,6 +24,7 @@
 // hipcc --offload-arch=gfx950, see native/build.py.
 
 #include <algorithm>
+#include <chrono>
 #include <cstdint>
 #include <initializer_list>
 #include <cstring>
@@ -682,6 +686,407 @@ py::dict cu_sweep_reference() {
     return out;
 }
 
+// ---------------- HBM scrub ----------------
+
+constexpr long long kScrubDefaultSlabBytes = 4ll << 30;
+constexpr long long kScrubMaxSlabBytes = 64ll << 30;
+constexpr long long kScrubMaxSlabs = 65536;
+constexpr long long kScrubMaxData = 1ll << 21;  // elements for return_data
+constexpr long long kScrubMaxRecords = 4096;
+// twice the Infinity Cache: from here on a line is read back from HBM
+constexpr unsigned long long kScrubBeyondCacheBytes = 512ull << 20;
+constexpr long long kMarchReferenceMaxCount = 1ll << 24;
+
+int march_pattern_by_name(const std::string &name) {
+    for (int p = 0; p < hbmmarch::kPatterns; ++p)
+        if (name == hbmmarch::kPatternNames[p]) return p;
+    throw std::invalid_argument("unknown pattern '" + name +
+                                "' (address, solid, checker, random)");
+}
+
+const char *march_mode_name(int mode) {
+    return mode == kMarchWrite ? "march_write"
+           : mode == kMarchRW  ? "march_rw"
+                               : "march_read";
+}
+
+// guard + n + guard elements of device memory, freed on scope exit
+struct ScrubSlab {
+    char *alloc = nullptr;
+    size_t n = 0;                  // elements under test
+    unsigned long long base = 0;   // global index of the first
+};
+
+struct ScrubSlabs {
+    std::vector<ScrubSlab> slabs;
+    ~ScrubSlabs() {
+        for (ScrubSlab &s : slabs) (void)hipFree(s.alloc);
+    }
+};
+
+struct ScrubCorruption {
+    enum Kind { kFlip, kAlias } kind;
+    int pattern;
+    long long after_step, element, word, bit, distance;
+};
+
+const char *const kScrubCorruptForm =
+    "corrupt must be (pattern, after_step, 'flip', element, word, bit) or "
+    "(pattern, after_step, 'alias', element, distance), or a list of such";
+
+ScrubCorruption parse_scrub_corruption(const py::sequence &seq,
+                                       const std::vector<int> &pats,
+                                       long long n) {
+    if (py::len(seq) < 5) throw std::invalid_argument(kScrubCorruptForm);
+    ScrubCorruption c{};
+    c.pattern = march_pattern_by_name(seq[0].cast<std::string>());
+    if (std::find(pats.begin(), pats.end(), c.pattern) == pats.end())
+        throw std::invalid_argument("corrupt: that pattern is not run");
+    c.after_step = seq[1].cast<long long>();
+    if (c.after_step < 0 || c.after_step > 2)
+        throw std::invalid_argument("corrupt: after_step must be in 0..2");
+    const std::string what = seq[2].cast<std::string>();
+    c.element = seq[3].cast<long long>();
+    if (c.element < 0 || c.element >= n)
+        throw std::invalid_argument("corrupt: element must be in 0..n-1");
+    if (what == "flip" && py::len(seq) == 6) {
+        c.kind = ScrubCorruption::kFlip;
+        c.word = seq[4].cast<long long>();
+        c.bit = seq[5].cast<long long>();
+        if (c.word < 0 || c.word > 3 || c.bit < 0 || c.bit > 31)
+            throw std::invalid_argument("flip: word in 0..3, bit in 0..31");
+    } else if (what == "alias" && py::len(seq) == 5) {
+        c.kind = ScrubCorruption::kAlias;
+        c.distance = seq[4].cast<long long>();
+        if (c.distance == 0 || c.distance <= -n || c.distance >= n ||
+            c.element + c.distance < 0 || c.element + c.distance >= n)
+            throw std::invalid_argument(
+                "alias: element + distance must be another element");
+    } else {
+        throw std::invalid_argument(kScrubCorruptForm);
+    }
+    return c;
+}
+
+void launch_march(u32x4 *data, const MarchParams &a, MarchReport *rep,
+                  MarchRecord *records, uint32_t *range_bad) {
+    const dim3 grid((unsigned)hbm_copy_blocks(a.n)), block(256);
+    switch (march_mode_of_step(a.step)) {
+    case kMarchWrite:
+        hipLaunchKernelGGL((march_kernel<kMarchWrite>), grid, block, 0, 0, data,
+                           a, rep, records, range_bad);
+        break;
+    case kMarchRW:
+        hipLaunchKernelGGL((march_kernel<kMarchRW>), grid, block, 0, 0, data, a,
+                           rep, records, range_bad);
+        break;
+    default:
+        hipLaunchKernelGGL((march_kernel<kMarchRead>), grid, block, 0, 0, data,
+                           a, rep, records, range_bad);
+    }
+    HIP_CHECK(hipGetLastError());
+}
+
+// In-place march test (hbm_march.h) of `bytes` of device memory, allocated
+// in slabs of at most slab_bytes, each between two poisoned guard bands of
+// `guard` elements.  Each step runs over ALL slabs before the next starts,
+// so between the write of a line and its read-back the whole region has
+// moved through the caches.  A slab that cannot be allocated ends the
+// allocation; what was obtained is tested.
+// corrupt = (pattern, after_step, "flip", element, word, bit) or
+//           (pattern, after_step, "alias", element, distance),
+//           or a list of such,
+// damages memory from the host, with hipMemcpy and no kernel, between step
+// after_step of that pattern and the step that follows; element is global.
+py::dict hbm_scrub(int device, long long bytes, long long slab_bytes,
+                   long long guard, py::object patterns,
+                   unsigned long long seed, py::object corrupt,
+                   long long max_records, bool return_data) {
+    if (bytes < 16 || bytes % 16)
+        throw std::invalid_argument("bytes must be a positive multiple of 16");
+    if (slab_bytes < 16 || slab_bytes % 16 || slab_bytes > kScrubMaxSlabBytes)
+        throw std::invalid_argument(
+            "slab_bytes must be a multiple of 16 in 16..64 GiB");
+    if ((bytes + slab_bytes - 1) / slab_bytes > kScrubMaxSlabs)
+        throw std::invalid_argument("bytes / slab_bytes must be at most 65536");
+    if (guard < 0 || guard > kCopyCheckMaxGuard)
+        throw std::invalid_argument("guard must be in 0..2^20 float4s");
+    if (max_records < 1 || max_records > kScrubMaxRecords)
+        throw std::invalid_argument("max_records must be in 1..4096");
+    const long long n_req = bytes / 16, slab_elems = slab_bytes / 16;
+    if (return_data && n_req > kScrubMaxData)
+        throw std::invalid_argument("return_data needs bytes <= 16 * 2^21");
+
+    std::vector<int> pats;
+    if (patterns.is_none()) {
+        for (int p = 0; p < hbmmarch::kPatterns; ++p) pats.push_back(p);
+    } else try {
+        for (py::handle h : patterns.cast<py::sequence>()) {
+            const int p = march_pattern_by_name(h.cast<std::string>());
+            if (std::find(pats.begin(), pats.end(), p) != pats.end())
+                throw std::invalid_argument("a pattern is given twice");
+            pats.push_back(p);
+        }
+        if (pats.empty())
+            throw std::invalid_argument("patterns must name at least one");
+    } catch (const py::cast_error &) {
+        throw std::invalid_argument("patterns must be a sequence of names");
+    }
+
+    // one corruption, or a list of them
+    std::vector<ScrubCorruption> damage;
+    if (!corrupt.is_none()) try {
+        py::sequence seq = corrupt.cast<py::sequence>();
+        if (py::len(seq) && py::isinstance<py::str>(seq[0])) {
+            damage.push_back(parse_scrub_corruption(seq, pats, n_req));
+        } else {
+            if (!py::len(seq)) throw std::invalid_argument(kScrubCorruptForm);
+            for (py::handle one : seq)
+                damage.push_back(parse_scrub_corruption(
+                    one.cast<py::sequence>(), pats, n_req));
+        }
+    } catch (const py::cast_error &) {
+        throw std::invalid_argument(kScrubCorruptForm);
+    } catch (const py::type_error &) {
+        throw std::invalid_argument(kScrubCorruptForm);
+    }
+
+    HIP_CHECK(hipSetDevice(device));
+    size_t free_before = 0, total_mem = 0;
+    HIP_CHECK(hipMemGetInfo(&free_before, &total_mem));
+
+    const auto wall_start = std::chrono::steady_clock::now();
+    ScrubSlabs owned;
+    std::vector<ScrubSlab> &slabs = owned.slabs;
+    const size_t guard_bytes = (size_t)guard * 16;
+    unsigned long long n_total = 0;
+    while (n_total < (unsigned long long)n_req) {
+        ScrubSlab s;
+        s.n = (size_t)std::min<unsigned long long>(slab_elems, n_req - n_total);
+        s.base = n_total;
+        const size_t alloc_bytes = 2 * guard_bytes + s.n * 16;
+        if (hipMalloc(reinterpret_cast<void **>(&s.alloc), alloc_bytes) !=
+            hipSuccess) {
+            (void)hipGetLastError();  // clear it: test what was obtained
+            break;
+        }
+        slabs.push_back(s);
+        n_total += s.n;
+        HIP_CHECK(hipMemset(s.alloc, hbmpattern::kPoisonByte, alloc_bytes));
+    }
+    if (slabs.empty())
+        throw std::runtime_error("hbm_scrub: no slab could be allocated");
+    for (const ScrubCorruption &c : damage)
+        if ((unsigned long long)c.element >= n_total ||
+            (unsigned long long)(c.element + c.distance) >= n_total)
+            throw std::runtime_error(
+                "hbm_scrub: corrupt names an element beyond what was allocated");
+    auto data_of = [&](const ScrubSlab &s) {
+        return reinterpret_cast<u32x4 *>(s.alloc + guard_bytes);
+    };
+    auto address_of = [&](unsigned long long elem) {
+        const ScrubSlab &s = slabs[elem / slab_elems];
+        return reinterpret_cast<char *>(data_of(s)) + (elem - s.base) * 16;
+    };
+
+    const size_t n_ranges =
+        (size_t)((n_total + (1ull << kMarchRangeShift) - 1) >> kMarchRangeShift);
+    DeviceBuffer<MarchReport> d_rep(1);
+    DeviceBuffer<MarchRecord> d_rec((size_t)max_records);
+    DeviceBuffer<uint32_t> d_ranges(n_ranges);
+    MarchReport rep{};
+    rep.first_bad = ~0ull;
+    HIP_CHECK(hipMemcpy(d_rep.get(), &rep, sizeof(rep), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemset(d_rec.get(), 0, (size_t)max_records * sizeof(MarchRecord)));
+    HIP_CHECK(hipMemset(d_ranges.get(), 0, n_ranges * sizeof(uint32_t)));
+    HIP_CHECK(hipDeviceSynchronize());
+
+    double mode_ms[3] = {0, 0, 0}, mode_bytes[3] = {0, 0, 0};
+    EventPair ev;
+    for (int p : pats) {
+        for (int step = 0; step < hbmmarch::kSteps; ++step) {
+            HIP_CHECK(hipEventRecord(ev.start));
+            for (size_t k = 0; k < slabs.size(); ++k) {
+                // the descending step also takes the slabs from the top
+                const ScrubSlab &s =
+                    slabs[hbmmarch::step_descends(step) ? slabs.size() - 1 - k : k];
+                MarchParams a;
+                a.pattern = p;
+                a.step = step;
+                a.seed = seed;
+                a.base = s.base;
+                a.n = s.n;
+                a.max_records = (uint32_t)max_records;
+                launch_march(data_of(s), a, d_rep.get(), d_rec.get(),
+                             d_ranges.get());
+            }
+            HIP_CHECK(hipEventRecord(ev.stop));
+            HIP_CHECK(hipEventSynchronize(ev.stop));
+            float ms = 0;
+            HIP_CHECK(hipEventElapsedTime(&ms, ev.start, ev.stop));
+            const int mode = march_mode_of_step(step);
+            mode_ms[mode] += ms;
+            mode_bytes[mode] += (mode == kMarchRW ? 2.0 : 1.0) * 16.0 * n_total;
+
+            for (const ScrubCorruption &c : damage) {
+                if (c.pattern != p || c.after_step != step) continue;
+                if (c.kind == ScrubCorruption::kFlip) {
+                    char *word = address_of(c.element) + 4 * c.word;
+                    uint32_t w = 0;
+                    HIP_CHECK(hipMemcpy(&w, word, sizeof(w), hipMemcpyDeviceToHost));
+                    w ^= 1u << c.bit;
+                    HIP_CHECK(hipMemcpy(word, &w, sizeof(w), hipMemcpyHostToDevice));
+                } else {
+                    HIP_CHECK(hipMemcpy(address_of(c.element),
+                                        address_of(c.element + c.distance), 16,
+                                        hipMemcpyDeviceToDevice));
+                }
+                HIP_CHECK(hipDeviceSynchronize());
+            }
+        }
+    }
+
+    HIP_CHECK(hipMemcpy(&rep, d_rep.get(), sizeof(rep), hipMemcpyDeviceToHost));
+    const size_t n_rec = std::min<size_t>(rep.n_records, (size_t)max_records);
+    std::vector<MarchRecord> h_rec(n_rec);
+    if (n_rec)
+        HIP_CHECK(hipMemcpy(h_rec.data(), d_rec.get(),
+                            n_rec * sizeof(MarchRecord), hipMemcpyDeviceToHost));
+    std::vector<uint32_t> h_ranges(n_ranges);
+    HIP_CHECK(hipMemcpy(h_ranges.data(), d_ranges.get(),
+                        n_ranges * sizeof(uint32_t), hipMemcpyDeviceToHost));
+
+    bool guard_ok = true;
+    std::vector<unsigned char> band(guard_bytes);
+    for (const ScrubSlab &s : slabs) {
+        if (band.empty()) break;
+        for (const char *from : {(const char *)s.alloc,
+                                 (const char *)s.alloc + guard_bytes + s.n * 16}) {
+            HIP_CHECK(hipMemcpy(band.data(), from, band.size(),
+                                hipMemcpyDeviceToHost));
+            for (unsigned char b : band)
+                if (b != hbmpattern::kPoisonByte) guard_ok = false;
+        }
+    }
+    const double wall_ms =
+        std::chrono::duration<double, std::milli>(
+            std::chrono::steady_clock::now() - wall_start).count();
+
+    auto record_dict = [](const MarchRecord &r) {
+        py::dict d;
+        d["pattern"] = r.pattern < (uint32_t)hbmmarch::kPatterns
+                           ? hbmmarch::kPatternNames[r.pattern] : "?";
+        d["step"] = r.step;
+        d["index"] = r.index;
+        d["word"] = r.word;
+        d["got"] = r.got;
+        d["expected"] = r.expected;
+        return d;
+    };
+    py::list records;
+    for (const MarchRecord &r : h_rec) records.append(record_dict(r));
+
+    // 2 MiB-aligned ranges of the scrub's byte offsets with a bad element,
+    // neighbours merged
+    py::list bad_ranges;
+    for (size_t lo = 0; lo < n_ranges; ++lo) {
+        if (!h_ranges[lo]) continue;
+        size_t hi = lo;
+        unsigned long long count = 0;
+        while (hi < n_ranges && h_ranges[hi]) count += h_ranges[hi++];
+        const unsigned long long first_elem = (unsigned long long)lo
+                                              << kMarchRangeShift;
+        const unsigned long long end_elem = std::min<unsigned long long>(
+            (unsigned long long)hi << kMarchRangeShift, n_total);
+        py::dict r;
+        r["start"] = first_elem * 16;
+        r["end"] = end_elem * 16 - 1;  // inclusive
+        r["mismatches"] = count;
+        r["slab"] = first_elem / slab_elems;
+        r["device_address"] = (unsigned long long)(uintptr_t)address_of(first_elem);
+        const MarchRecord *first = nullptr;  // the lowest record in the range
+        for (const MarchRecord &rec : h_rec)
+            if (rec.index >= first_elem && rec.index < end_elem &&
+                (!first || rec.index < first->index))
+                first = &rec;
+        r["first"] = first ? py::object(record_dict(*first)) : py::none();
+        bad_ranges.append(r);
+        lo = hi;
+    }
+
+    py::dict steps;
+    double scrub_ms = 0;
+    for (int mode = 0; mode < 3; ++mode) {
+        py::dict m;
+        m["bytes"] = (unsigned long long)mode_bytes[mode];
+        m["ms"] = mode_ms[mode];
+        m["gbps"] = mode_ms[mode] > 0 ? mode_bytes[mode] / (mode_ms[mode] * 1e6) : 0.0;
+        steps[march_mode_name(mode)] = m;
+        scrub_ms += mode_ms[mode];
+    }
+    py::list pattern_names;
+    for (int p : pats) pattern_names.append(hbmmarch::kPatternNames[p]);
+
+    py::dict out;
+    out["bytes_requested"] = bytes;
+    out["bytes_tested"] = n_total * 16;
+    out["slabs"] = slabs.size();
+    out["slab_bytes"] = slab_bytes;
+    out["guard"] = guard;
+    out["patterns"] = pattern_names;
+    out["seed"] = seed;
+    out["vram_bytes"] = (uint64_t)total_mem;
+    out["vram_free_before"] = (uint64_t)free_before;
+    out["mismatches"] = rep.mismatches;
+    out["first_bad"] = rep.mismatches ? (long long)rep.first_bad : -1;
+    out["bad_bits"] = py::make_tuple(rep.bad_bits[0], rep.bad_bits[1],
+                                     rep.bad_bits[2], rep.bad_bits[3]);
+    out["records"] = records;
+    out["bad_ranges"] = bad_ranges;
+    out["guard_ok"] = guard_ok;
+    out["beyond_cache"] = n_total * 16 >= kScrubBeyondCacheBytes;
+    out["scrub_ms"] = scrub_ms;
+    out["wall_ms"] = wall_ms;  // allocation, poison and guard check included
+    out["steps"] = steps;
+    out["poison_byte"] = hbmpattern::kPoisonByte;
+    out["ok"] = rep.mismatches == 0 && guard_ok;
+    if (return_data) {
+        py::list data;  // per slab, guard bands included
+        for (const ScrubSlab &s : slabs) {
+            std::vector<char> all(2 * guard_bytes + s.n * 16);
+            HIP_CHECK(hipMemcpy(all.data(), s.alloc, all.size(),
+                                hipMemcpyDeviceToHost));
+            data.append(py::bytes(all.data(), all.size()));
+        }
+        out["data"] = data;
+    }
+    return out;
+}
+
+// hbmmarch::expected for elements start..start+count-1 as bytes: no HIP
+// call, works without a GPU.
+py::bytes hbm_march_reference(const std::string &pattern,
+                              unsigned long long seed, int step,
+                              unsigned long long start, long long count) {
+    const int p = march_pattern_by_name(pattern);
+    if (step < 0 || step >= hbmmarch::kSteps)
+        throw std::invalid_argument("step must be in 0..3");
+    if (count < 0 || count > kMarchReferenceMaxCount)
+        throw std::invalid_argument("count must be in 0..2^24");
+    std::vector<hbmmarch::Element> out((size_t)count);
+    for (long long k = 0; k < count; ++k)
+        out[(size_t)k] = hbmmarch::expected(p, seed, step, start + k);
+    return py::bytes((const char *)out.data(), out.size() * sizeof(out[0]));
+}
+
+// (free, total) bytes of device memory, hipMemGetInfo.
+py::tuple mem_info(int device) {
+    HIP_CHECK(hipSetDevice(device));
+    size_t free_bytes = 0, total = 0;
+    HIP_CHECK(hipMemGetInfo(&free_bytes, &total));
+    return py::make_tuple((uint64_t)free_bytes, (uint64_t)total);
+}
+
 int device_count() {
     int n = 0;
     hipError_t e = hipGetDeviceCount(&n);
@@ -772,4 +1177,13 @@ PYBIND11_MODULE(_healthprobe, m) {
     m.def("cu_sweep_reference", &cu_sweep_reference);
     m.def("decode_hw_id", &decode_hw_id_py, py::arg("hw_id"),
           py::arg("xcc_id"));
+    m.def("hbm_scrub", &hbm_scrub, py::arg("device") = 0,
+          py::arg("bytes") = (long long)1 << 30,
+          py::arg("slab_bytes") = kScrubDefaultSlabBytes,
+          py::arg("guard") = 4096, py::arg("patterns") = py::none(),
+          py::arg("seed") = 0x5EEDull, py::arg("corrupt") = py::none(),
+          py::arg("max_records") = 64, py::arg("return_data") = false);
+    m.def("hbm_march_reference", &hbm_march_reference, py::arg("pattern"),
+          py::arg("seed"), py::arg("step"), py::arg("start"), py::arg("count"));
+    m.def("mem_info", &mem_info, py::arg("device") = 0);
 }

@@ -7,6 +7,7 @@
 
 #include <cstdint>
 
+#include "hbm_march.h"
 #include "hbm_pattern.h"
 #include "sweep_table.h"
 
@@ -216,6 +217,149 @@ __global__ void verify_pattern_kernel(const float4 *__restrict__ buf, size_t n,
         atomicAdd(mismatches, bad);
         atomicMin(first_bad, first);
     }
+}
+
+// ---------------- HBM scrub: in-place march over one slab ----------------
+
+// What the march kernels of one scrub report into; the host zeroes it and
+// sets first_bad = ~0 before the first launch.
+struct MarchReport {
+    unsigned long long mismatches;  // elements that read back wrong
+    unsigned long long first_bad;   // lowest such global index
+    uint32_t bad_bits[4];           // OR of got ^ expected, per word
+    uint32_t n_records;             // slots claimed, may pass max_records
+    uint32_t reserved;
+};
+
+// One wrong element, written into a claimed slot with ordinary stores.
+struct MarchRecord {
+    uint32_t pattern, step;
+    unsigned long long index;  // global element index
+    uint32_t word;             // lowest differing word
+    uint32_t got, expected;    // that word
+    uint32_t reserved;
+};
+
+// Elements per entry of the per-range counters: 2 MiB of 16-byte elements.
+constexpr int kMarchRangeShift = 17;
+
+// One launch: which step of which pattern, over which slab.
+struct MarchParams {
+    int pattern, step;              // hbmmarch::Pattern, 0..3
+    unsigned long long seed;
+    unsigned long long base;        // global index of the slab's element 0
+    size_t n;                       // elements of this slab
+    uint32_t max_records;
+};
+
+using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
+
+enum MarchMode { kMarchWrite = 0, kMarchRW = 1, kMarchRead = 2 };
+
+// The cold path: element `index` read back as got, not as want.
+__device__ __noinline__ void march_report(u32x4 got, u32x4 want,
+                                          unsigned long long index,
+                                          uint32_t pattern, uint32_t step,
+                                          uint32_t max_records, MarchReport *rep,
+                                          MarchRecord *records,
+                                          uint32_t *range_bad) {
+    // no array indexed at run time: that would cost the kernel scratch memory
+    const uint32_t d0 = got.x ^ want.x, d1 = got.y ^ want.y,
+                   d2 = got.z ^ want.z, d3 = got.w ^ want.w;
+    atomicAdd(&rep->mismatches, 1ull);
+    atomicMin(&rep->first_bad, index);
+    if (d0) atomicOr(&rep->bad_bits[0], d0);
+    if (d1) atomicOr(&rep->bad_bits[1], d1);
+    if (d2) atomicOr(&rep->bad_bits[2], d2);
+    if (d3) atomicOr(&rep->bad_bits[3], d3);
+    const int word = d0 ? 0 : d1 ? 1 : d2 ? 2 : 3;
+    const uint32_t got_word = d0 ? got.x : d1 ? got.y : d2 ? got.z : got.w;
+    atomicAdd(&range_bad[index >> kMarchRangeShift], 1u);
+    // the plain read keeps a wholly bad slab from wrapping the counter
+    if (*(volatile uint32_t *)&rep->n_records < max_records) {
+        const uint32_t slot = atomicAdd(&rep->n_records, 1u);
+        if (slot < max_records) {
+            MarchRecord r;
+            r.pattern = pattern;
+            r.step = step;
+            r.index = index;
+            r.word = (uint32_t)word;
+            r.got = got_word;
+            r.expected = got_word ^ (d0 ? d0 : d1 ? d1 : d2 ? d2 : d3);
+            r.reserved = 0;
+            records[slot] = r;
+        }
+    }
+}
+
+// One march step (hbm_march.h) over one slab, in place, in the shape of
+// hbm_copy_kernel: 16 B per lane, work item j of the slab's n handles
+// element j (n - 1 - j in the descending step), thread t takes the work
+// items t + k * stride, k = 0..3, with its four nontemporal loads in flight
+// before the first compare and store; threads whose fourth item would pass
+// n fall to the grid-stride tail.  kMarchWrite (step 0) only stores,
+// kMarchRead (step 3) only loads and compares, kMarchRW (steps 1, 2) loads,
+// compares with hbmmarch::expected_of and stores hbmmarch::to_write_of to
+// the same address.  NT = false gives plain stores and loads (hbm_bench).
+// PRECONDITION, as for hbm_copy_kernel: 4 * gridDim.x * blockDim.x >= n.
+template <int MODE, bool NT = true>
+__global__ void march_kernel(u32x4 *__restrict__ slab, MarchParams a,
+                             MarchReport *rep, MarchRecord *records,
+                             uint32_t *range_bad) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool down = hbmmarch::step_descends(a.step);
+    auto element = [&](size_t j) { return down ? a.n - 1 - j : j; };
+    auto load = [&](size_t e) {
+        return NT ? __builtin_nontemporal_load(&slab[e]) : slab[e];
+    };
+    // the pattern once per element; check and store derive from it
+    auto finish = [&](size_t e, u32x4 got) {
+        const hbmmarch::Element p =
+            hbmmarch::pattern(a.pattern, a.seed, a.base + e);
+        if (MODE != kMarchWrite) {
+            const hbmmarch::Element v = hbmmarch::expected_of(p, a.step);
+            const u32x4 want = {v.w[0], v.w[1], v.w[2], v.w[3]};
+            if ((got.x ^ want.x) | (got.y ^ want.y) | (got.z ^ want.z) |
+                (got.w ^ want.w))
+                march_report(got, want, a.base + e, (uint32_t)a.pattern,
+                             (uint32_t)a.step, a.max_records, rep, records,
+                             range_bad);
+        }
+        if (MODE != kMarchRead) {
+            const hbmmarch::Element v = hbmmarch::to_write_of(p, a.step);
+            const u32x4 x = {v.w[0], v.w[1], v.w[2], v.w[3]};
+            if (NT)
+                __builtin_nontemporal_store(x, &slab[e]);
+            else
+                slab[e] = x;
+        }
+    };
+    const u32x4 none = {0, 0, 0, 0};
+    if (t + 3 * stride < a.n) {
+        const size_t e0 = element(t), e1 = element(t + stride),
+                     e2 = element(t + 2 * stride), e3 = element(t + 3 * stride);
+        u32x4 g0 = none, g1 = none, g2 = none, g3 = none;
+        if (MODE != kMarchWrite) {
+            g0 = load(e0);
+            g1 = load(e1);
+            g2 = load(e2);
+            g3 = load(e3);
+        }
+        finish(e0, g0);
+        finish(e1, g1);
+        finish(e2, g2);
+        finish(e3, g3);
+    } else {
+        for (size_t j = t; j < a.n; j += stride) {
+            const size_t e = element(j);
+            finish(e, MODE != kMarchWrite ? load(e) : none);
+        }
+    }
+}
+
+constexpr int march_mode_of_step(int step) {
+    return step == 0 ? kMarchWrite : step == 3 ? kMarchRead : kMarchRW;
 }
 
 // ---------------- CU sweep: known-answer MFMA on every SIMD ----------------

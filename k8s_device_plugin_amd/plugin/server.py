@@ -214,10 +214,14 @@ class AMDGPUPlugin:
             run_cu_sweep,
         )
 
+        # hbm_scrub_bytes=0: never the HBM scrub here, whatever
+        # AMDXDP_HBM_SCRUB_BYTES says; on a live node the pods own the VRAM
         if not self.deep_cu_sweep:
-            return deep_health_probe(device=self._hip_ordinal(dev))
+            return deep_health_probe(device=self._hip_ordinal(dev),
+                                     hbm_scrub_bytes=0)
         ordinals = self._hip_ordinals(dev)
-        res = deep_health_probe(device=ordinals[0], cu_sweep=False)
+        res = deep_health_probe(device=ordinals[0], cu_sweep=False,
+                                hbm_scrub_bytes=0)
         res["cu_sweep"] = {}
         bad_simds = 0
         for ordinal in ordinals:
