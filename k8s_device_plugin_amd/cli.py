@@ -69,6 +69,11 @@ def device_plugin_main(argv=None) -> int:
                          "run exact known-answer matrix products on every "
                          "SIMD of every CU, on every HIP device of the GPU, "
                          "and pin a GPU with a bad SIMD Unhealthy")
+    ap.add_argument("--deep-probe-lds-sweep", action="store_true",
+                    help="with --deep-probe-every / --prestart-deep: also "
+                         "march-test the whole LDS of every CU through every "
+                         "route into it, on every HIP device of the GPU, and "
+                         "pin a GPU with a bad CU Unhealthy")
     ap.add_argument("--dump", action="store_true",
                     help="print discovered devices + allocator state as "
                          "JSON and exit (debugging)")
@@ -198,6 +203,7 @@ def device_plugin_main(argv=None) -> int:
                                  prestart_deep=args.prestart_deep,
                                  deep_probe_every=args.deep_probe_every,
                                  deep_cu_sweep=args.deep_probe_cu_sweep,
+                                 deep_lds_sweep=args.deep_probe_lds_sweep,
                                  exit_on_stream_loss=args.exit_on_stream_loss),
         device_plugin_path=args.kubelet_dir or dp.DEVICE_PLUGIN_PATH,
         server_impl=args.server,

@@ -139,6 +139,58 @@ def run_cu_sweep(device: int = 0, mod=None) -> dict:
     return mod.cu_sweep(device=device, inject=_sweep_inject_from_env())
 
 
+LDS_SWEEP_ENV = "AMDXDP_LDS_SWEEP"
+LDS_SWEEP_INJECT_ENV = "AMDXDP_LDS_SWEEP_INJECT"
+
+
+def lds_sweep_enabled(lds_sweep: Optional[bool] = None) -> bool:
+    """An explicit argument wins; None reads AMDXDP_LDS_SWEEP (unset, empty
+    or 0 = off)."""
+    if lds_sweep is not None:
+        return bool(lds_sweep)
+    return os.environ.get(LDS_SWEEP_ENV, "0").strip() not in ("", "0")
+
+
+def _lds_inject_from_env():
+    """AMDXDP_LDS_SWEEP_INJECT="block:element:word:bit" -> the corruption
+    that flips that bit of that block's LDS after step 0 of the first
+    pattern of path b128: one bad LDS cell simulated on healthy hardware."""
+    spec = os.environ.get(LDS_SWEEP_INJECT_ENV, "").strip()
+    if not spec:
+        return None
+    try:
+        block, element, word, bit = (int(x) for x in spec.split(":"))
+    except ValueError:
+        raise ValueError(
+            f"{LDS_SWEEP_INJECT_ENV}={spec!r}: expected block:element:word:bit"
+        ) from None
+    return (block, "b128", "address", 0, "flip", element, word, bit)
+
+
+def lds_sweep_violations(sweep: dict) -> list:
+    """One line per CU whose LDS failed the sweep."""
+    lines = []
+    for b in sweep.get("bad", []):
+        line = "lds_sweep: xcc {} se {} cu {}: {} bad accesses".format(
+            b["xcc"], b["se"], b["cu"], b["mismatches"])
+        first = b.get("first")
+        if first:
+            line += (" (path {} pattern {} step {}, element {}, bits {:#010x}"
+                     " in word {})").format(
+                first["path"], first["pattern"], first["step"],
+                first["element"], first["got"] ^ first["expected"],
+                first["word"])
+        lines.append(line)
+    return lines
+
+
+def run_lds_sweep(device: int = 0, mod=None) -> dict:
+    """March test of the whole LDS of every CU of one HIP device."""
+    if mod is None:
+        mod = load_healthprobe(required=True)
+    return mod.lds_sweep(device=device, corrupt=_lds_inject_from_env())
+
+
 HBM_SCRUB_ENV = "AMDXDP_HBM_SCRUB_BYTES"
 HBM_SCRUB_DEFAULT_RESERVE = 2 << 30
 # below this share of the card's VRAM a scrub of "all" says that it was partial
@@ -169,12 +221,13 @@ def hbm_scrub_bytes_from_env(hbm_scrub_bytes=None):
     return spec or None
 
 
-def read_ecc_counts(bdf: str, sysroot: str = "/"):
+def read_ecc_counts(bdf: str, sysroot: str = "/", block: str = "umc"):
     """{"ue": n, "ce": n} from <sysroot>/sys/bus/pci/devices/<bdf>/ras/
-    umc_err_count (lines of `key: integer`, other keys ignored), or None when
-    the file cannot be read or does not hold both."""
+    <block>_err_count (lines of `key: integer`, other keys ignored), or None
+    when the file cannot be read or does not hold both.  block: "umc" is the
+    HBM's counters, "gfx" those of the compute units, LDS included."""
     path = os.path.join(sysroot, "sys/bus/pci/devices", bdf, "ras",
-                        "umc_err_count")
+                        f"{block}_err_count")
     counts = {}
     try:
         with open(path) as f:
@@ -257,6 +310,45 @@ def hbm_scrub(device: int = 0, bytes=None,
     return res
 
 
+def lds_sweep_with_ecc(device: int = 0, mod=None, sysroot: str = "/") -> dict:
+    """run_lds_sweep between two readings of the GPU's gfx RAS counters.
+
+    Adds `violations`, `warnings` and `ecc` (gfx_err_count before and after,
+    None when unreadable) to the module's result: LDS is ECC-protected, so a
+    weak cell may show only as a corrected error.
+    """
+    if mod is None:
+        mod = load_healthprobe(required=True)
+    bdf = None
+    try:
+        bdf = mod.pci_bus_ids()[device].lower()
+    except Exception:
+        pass
+    ecc_before = read_ecc_counts(bdf, sysroot, "gfx") if bdf else None
+    res = run_lds_sweep(device, mod)
+    ecc_after = read_ecc_counts(bdf, sysroot, "gfx") if bdf else None
+
+    violations = lds_sweep_violations(res)
+    warnings = []
+    if res.get("ok") and not res.get("coverage_complete"):
+        warnings.append("lds_sweep_incomplete: {} of {} CUs".format(
+            res.get("cus_covered"), res.get("cu_count")))
+    res["ecc"] = None
+    if ecc_before is not None and ecc_after is not None:
+        res["ecc"] = {"before": ecc_before, "after": ecc_after}
+        ue = ecc_after["ue"] - ecc_before["ue"]
+        ce = ecc_after["ce"] - ecc_before["ce"]
+        if ue > 0:
+            violations.append(
+                f"lds_sweep: {ue} uncorrectable gfx ECC errors during the sweep")
+        if ce > 0:
+            warnings.append(
+                f"lds_sweep_ecc: {ce} corrected gfx ECC errors during the sweep")
+    res["violations"] = violations
+    res["warnings"] = warnings
+    return res
+
+
 def deep_health_probe(
     device: int = 0,
     hbm_bytes: int = 1 << 30,
@@ -264,6 +356,8 @@ def deep_health_probe(
     hbm_floor_gbps: Optional[float] = None,
     cu_sweep: Optional[bool] = None,
     hbm_scrub_bytes=None,
+    lds_sweep: Optional[bool] = None,
+    sysroot: str = "/",
 ) -> dict:
     """Run the on-GPU MFMA/LDS/HBM probe and apply performance floors.
 
@@ -279,6 +373,13 @@ def deep_health_probe(
     hbm_scrub_bytes (None = env AMDXDP_HBM_SCRUB_BYTES, default off; "all" or
     a byte count) adds the march test of that much VRAM under `hbm_scrub`;
     its violations and warnings join `floor_violations` and `warnings`.
+
+    lds_sweep (None = env AMDXDP_LDS_SWEEP, default off) adds the march test
+    of every CU's whole LDS under `lds_sweep`: a CU with a bad access makes
+    the GPU unhealthy, with one violation line each; a clean sweep that did
+    not own every CU's LDS only warns.  The gfx RAS counters under sysroot
+    are read before and after (`ecc`, None when unreadable): corrected
+    errors during the sweep warn, uncorrectable ones are a violation.
     """
     if mfma_floor_tflops is None:
         mfma_floor_tflops = _floor_from_env(MFMA_FLOOR_ENV,
@@ -317,6 +418,12 @@ def deep_health_probe(
                     sweep.get("cus_covered"), sweep.get("cu_count"),
                     sweep.get("simds_covered"))
             ]
+    if lds_sweep_enabled(lds_sweep):
+        sweep = lds_sweep_with_ecc(device, mod, sysroot)
+        res["lds_sweep"] = sweep
+        violations.extend(sweep["violations"])
+        if sweep["warnings"]:
+            res.setdefault("warnings", []).extend(sweep["warnings"])
     scrub_bytes = hbm_scrub_bytes_from_env(hbm_scrub_bytes)
     if scrub_bytes is not None:
         scrub = hbm_scrub(device, scrub_bytes, mod=mod)

@@ -15,7 +15,11 @@
 //      place each wave ran read from the hardware id registers;
 //   6. on request (hbm_scrub), in-place march passes over all free VRAM:
 //      fused read-verify-write at streaming rate, four data patterns and
-//      their complements (hbm_march.h).
+//      their complements (hbm_march.h);
+//   7. on request (lds_sweep), the same march over all 160 KiB of LDS of
+//      every CU, through the 128-, 64- and 32-bit loads and stores, the
+//      LDS-DMA and the transposed read (lds_march.h), with the place each
+//      block ran read from the hardware id registers.
 //
 // Used by the plugin's optional deep health check, __graft_entry__.smoke(),
 // and the gpu-marked tests.  The kernels live in probe_kernels.h (shared
@@ -1079,6 +1083,397 @@ py::bytes hbm_march_reference(const std::string &pattern,
     return py::bytes((const char *)out.data(), out.size() * sizeof(out[0]));
 }
 
+// ---------------- LDS sweep ----------------
+
+constexpr int kLdsSweepMaxLaunches = 4;
+constexpr long long kLdsSweepMaxArgBytes = 1ll << 30;
+
+int lds_path_by_name(const std::string &name) {
+    for (int p = 0; p < ldsmarch::kPaths; ++p)
+        if (name == ldsmarch::kPathNames[p]) return p;
+    throw std::invalid_argument("unknown path '" + name +
+                                "' (b128, b64, b32, dma, tr16)");
+}
+
+const char *const kLdsCorruptForm =
+    "corrupt must be (block, path, pattern, after_step, 'flip', element, word, "
+    "bit) or (block, path, pattern, after_step, 'alias', element, distance)";
+
+struct LdsCorruptSpec {
+    bool given = false;
+    long long block = -1, step = 0, element = 0, word = 0, bit = 0, distance = 0;
+    int path = 0, pattern = 0, kind = kLdsNone;
+};
+
+// The part of the corruption that depends on the sizes, which with
+// lds_bytes = 0 or blocks = 0 are known only once the card is.
+void check_lds_corruption(const LdsCorruptSpec &c, long long lds_bytes,
+                          long long blocks) {
+    if (!c.given) return;
+    if (blocks && c.block >= blocks)
+        throw std::invalid_argument("corrupt: block must be in 0..blocks-1");
+    if (!lds_bytes) return;
+    const long long n = ldsmarch::covered_bytes(c.path, (uint32_t)lds_bytes) / 16;
+    if (c.element >= n)
+        throw std::invalid_argument(
+            "corrupt: element must be inside the bytes the path covers");
+    if (c.kind == kLdsAlias &&
+        (c.element + c.distance < 0 || c.element + c.distance >= n))
+        throw std::invalid_argument(
+            "alias: element + distance must be another element that the path covers");
+}
+
+py::dict lds_first_failure(const ldsmarch::First &f, uint32_t expected) {
+    py::dict first;
+    first["path"] = f.path < (uint32_t)ldsmarch::kPaths
+                        ? ldsmarch::kPathNames[f.path] : "?";
+    first["pattern"] = hbmmarch::kPatternNames[f.pattern];
+    first["step"] = f.step;
+    first["element"] = f.element;
+    first["word"] = f.word;
+    first["got"] = f.got;
+    first["expected"] = expected;
+    return first;
+}
+
+// March test of a CU's LDS through every route into and out of it
+// (lds_sweep_kernel, lds_march.h), one block of lds_bytes per CU, with the
+// place each block ran read from the hardware id registers.  Where the
+// records show a CU that hosted no block, launch again with doubled reps,
+// at most kLdsSweepMaxLaunches in all, accumulating coverage and failures
+// (with fewer blocks than CUs there is nothing to wait for: one launch).
+// lds_bytes = 0: sharedMemPerBlock; blocks = 0: one per CU; reps = 0: the
+// default.  patterns names the patterns of the three march paths; dma is
+// defined with `random` and tr16 with `address`.
+// corrupt = (block, path, pattern, after_step, "flip", element, word, bit)
+//        or (block, path, pattern, after_step, "alias", element, distance)
+// makes thread 0 of that block damage its own LDS once per launch.
+py::dict lds_sweep(int device, long long lds_bytes, long long blocks,
+                   long long reps, py::object paths, py::object patterns,
+                   unsigned long long seed, py::object corrupt) {
+    if (lds_bytes < 0 || lds_bytes % 16 || lds_bytes > kLdsSweepMaxArgBytes)
+        throw std::invalid_argument(
+            "lds_bytes must be a multiple of 16 in 16..2^30 (0 = the card's "
+            "sharedMemPerBlock)");
+    if (blocks < 0 || blocks > 65536)
+        throw std::invalid_argument("blocks must be in 1..65536 (0 = cu_count)");
+    if (reps < 0 || reps > 65536)
+        throw std::invalid_argument("reps must be in 0..65536 (0 = default)");
+    if (reps == 0) reps = ldsmarch::kDefaultReps;
+
+    bool path_on[ldsmarch::kPaths] = {};
+    if (paths.is_none()) {
+        for (bool &on : path_on) on = true;
+    } else try {
+        bool any = false;
+        for (py::handle h : paths.cast<py::sequence>()) {
+            const int p = lds_path_by_name(h.cast<std::string>());
+            if (path_on[p]) throw std::invalid_argument("a path is given twice");
+            path_on[p] = any = true;
+        }
+        if (!any) throw std::invalid_argument("paths must name at least one");
+    } catch (const py::cast_error &) {
+        throw std::invalid_argument("paths must be a sequence of names");
+    } catch (const py::type_error &) {
+        throw std::invalid_argument("paths must be a sequence of names");
+    }
+    uint32_t march_mask = 0;  // 0: each path's default
+    if (!patterns.is_none()) try {
+        for (py::handle h : patterns.cast<py::sequence>()) {
+            const uint32_t bit =
+                ldsmarch::pattern_bit(march_pattern_by_name(h.cast<std::string>()));
+            if (march_mask & bit)
+                throw std::invalid_argument("a pattern is given twice");
+            march_mask |= bit;
+        }
+        if (!march_mask)
+            throw std::invalid_argument("patterns must name at least one");
+    } catch (const py::cast_error &) {
+        throw std::invalid_argument("patterns must be a sequence of names");
+    } catch (const py::type_error &) {
+        throw std::invalid_argument("patterns must be a sequence of names");
+    }
+    uint32_t mask_of[ldsmarch::kPaths];
+    for (int p = 0; p < ldsmarch::kPaths; ++p)
+        mask_of[p] = !path_on[p] ? 0
+                     : march_mask && !ldsmarch::pattern_is_fixed(p)
+                         ? march_mask
+                         : ldsmarch::default_patterns(p);
+
+    LdsCorruptSpec c;
+    if (!corrupt.is_none()) try {
+        py::sequence seq = corrupt.cast<py::sequence>();
+        const size_t len = py::len(seq);
+        if (len != 7 && len != 8) throw std::invalid_argument(kLdsCorruptForm);
+        c.given = true;
+        c.block = seq[0].cast<long long>();
+        c.path = lds_path_by_name(seq[1].cast<std::string>());
+        c.pattern = march_pattern_by_name(seq[2].cast<std::string>());
+        c.step = seq[3].cast<long long>();
+        const std::string what = seq[4].cast<std::string>();
+        c.element = seq[5].cast<long long>();
+        if (c.block < 0)
+            throw std::invalid_argument("corrupt: block must be in 0..blocks-1");
+        if (!(mask_of[c.path] >> c.pattern & 1))
+            throw std::invalid_argument(
+                "corrupt: that pattern does not run on that path");
+        if (c.step < 0 || c.step > 3 ||
+            !ldsmarch::step_is_followed_by_read(c.path, (int)c.step))
+            throw std::invalid_argument(
+                "corrupt: after_step must be a step of the path that a reading "
+                "step follows");
+        if (c.element < 0 || c.element >= kLdsSweepMaxArgBytes / 16)
+            throw std::invalid_argument(
+                "corrupt: element must be inside the bytes the path covers");
+        if (what == "flip" && len == 8) {
+            c.kind = kLdsFlip;
+            c.word = seq[6].cast<long long>();
+            c.bit = seq[7].cast<long long>();
+            if (c.word < 0 || c.word > 3 || c.bit < 0 || c.bit > 31)
+                throw std::invalid_argument("flip: word in 0..3, bit in 0..31");
+        } else if (what == "alias" && len == 7) {
+            c.kind = kLdsAlias;
+            c.distance = seq[6].cast<long long>();
+            if (c.distance == 0 || c.distance <= -kLdsSweepMaxArgBytes / 16 ||
+                c.distance >= kLdsSweepMaxArgBytes / 16)
+                throw std::invalid_argument(
+                    "alias: element + distance must be another element that "
+                    "the path covers");
+        } else {
+            throw std::invalid_argument(kLdsCorruptForm);
+        }
+        check_lds_corruption(c, lds_bytes, blocks);
+    } catch (const py::cast_error &) {
+        throw std::invalid_argument(kLdsCorruptForm);
+    } catch (const py::type_error &) {
+        throw std::invalid_argument(kLdsCorruptForm);
+    }
+
+    HIP_CHECK(hipSetDevice(device));
+    hipDeviceProp_t props;
+    HIP_CHECK(hipGetDeviceProperties(&props, device));
+    const int cu_count = props.multiProcessorCount;
+    const long long lds_bytes_per_cu = (long long)props.maxSharedMemoryPerMultiProcessor;
+    if (lds_bytes == 0) lds_bytes = (long long)props.sharedMemPerBlock / 16 * 16;
+    if (lds_bytes < 16 || (size_t)lds_bytes > props.sharedMemPerBlock ||
+        lds_bytes > (long long)ldsmarch::kMaxLdsBytes)
+        throw std::invalid_argument(
+            "lds_bytes is above this GPU's sharedMemPerBlock of " +
+            std::to_string(props.sharedMemPerBlock));
+    if (blocks == 0) blocks = cu_count;
+    check_lds_corruption(c, lds_bytes, blocks);
+
+    const uint32_t elems = (uint32_t)(lds_bytes / 16);
+    const uint32_t image_elems =
+        ldsmarch::covered_bytes(ldsmarch::kDma, (uint32_t)lds_bytes) / 16;
+    std::vector<hbmmarch::Element> image(std::max<uint32_t>(image_elems, 1));
+    for (uint32_t e = 0; e < image_elems; ++e)
+        image[e] = hbmmarch::pattern(hbmmarch::kRandom, seed, e);
+    DeviceBuffer<u32x4> d_image(image.size());
+    HIP_CHECK(hipMemcpy(d_image.get(), image.data(),
+                        image.size() * sizeof(image[0]), hipMemcpyHostToDevice));
+
+    LdsSweepParams a{};
+    a.lds_bytes = (uint32_t)lds_bytes;
+    for (int p = 0; p < ldsmarch::kPaths; ++p) a.patterns[p] = mask_of[p];
+    a.seed = seed;
+    a.image = d_image.get();
+    a.c_block = c.given ? (int)c.block : -1;
+    a.c_path = c.path;
+    a.c_pattern = c.pattern;
+    a.c_step = (int)c.step;
+    a.c_kind = c.kind;
+    a.c_element = (uint32_t)c.element;
+    a.c_word = (uint32_t)c.word;
+    a.c_bit = (uint32_t)c.bit;
+    a.c_distance = (int)c.distance;
+
+    const size_t n_rec = (size_t)blocks;
+    DeviceBuffer<LdsBlockRecord> d_rec(n_rec);
+    std::vector<LdsBlockRecord> h_rec(n_rec);
+    LdsBlockRecord blank{};
+    blank.first = ~0ull;
+    const std::vector<LdsBlockRecord> blanks(n_rec, blank);
+
+    using CuId = std::tuple<int, int, int, int>;  // xcc, se, sh, cu
+    struct Bad {
+        unsigned long long mismatches = 0;
+        uint32_t bits[4] = {0, 0, 0, 0};
+        unsigned long long first = ~0ull;
+        uint32_t block = 0;
+    };
+    std::map<CuId, unsigned> blocks_of_cu;
+    std::map<CuId, Bad> bad;
+    py::list records;
+    unsigned long long mismatches = 0;
+    double sweep_ms = 0;
+    int launches = 0;
+    bool covered = false, consistent = true;
+    EventPair ev;
+    while (launches < kLdsSweepMaxLaunches && !covered) {
+        if (launches) reps = std::min<long long>(reps * 2, 1 << 16);
+        ++launches;
+        a.reps = (int)reps;
+        HIP_CHECK(hipMemcpy(d_rec.get(), blanks.data(),
+                            n_rec * sizeof(LdsBlockRecord), hipMemcpyHostToDevice));
+        HIP_CHECK(hipEventRecord(ev.start));
+        hipLaunchKernelGGL(lds_sweep_kernel, dim3((unsigned)blocks),
+                           dim3(ldsmarch::kThreads), (size_t)lds_bytes, 0, a,
+                           d_rec.get());
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipEventRecord(ev.stop));
+        HIP_CHECK(hipEventSynchronize(ev.stop));
+        float ms = 0;
+        HIP_CHECK(hipEventElapsedTime(&ms, ev.start, ev.stop));
+        sweep_ms += ms;
+        HIP_CHECK(hipMemcpy(h_rec.data(), d_rec.get(),
+                            n_rec * sizeof(LdsBlockRecord), hipMemcpyDeviceToHost));
+
+        for (size_t b = 0; b < n_rec; ++b) {
+            const LdsBlockRecord &r = h_rec[b];
+            py::list slots;
+            for (uint32_t s = 0; s < std::min<uint32_t>(r.n_slots, kLdsSlots); ++s)
+                slots.append(py::make_tuple(r.slots[s].meta, r.slots[s].element,
+                                            r.slots[s].got, r.slots[s].expected));
+            records.append(py::make_tuple(
+                py::make_tuple(r.hw_id[0], r.hw_id[1], r.hw_id[2], r.hw_id[3]),
+                py::make_tuple(r.xcc_id[0], r.xcc_id[1], r.xcc_id[2], r.xcc_id[3]),
+                r.mismatches,
+                py::make_tuple(r.bad_bits[0], r.bad_bits[1], r.bad_bits[2],
+                               r.bad_bits[3]),
+                r.first, slots));
+            const SimdId w0 = decode_hw_id(r.hw_id[0], r.xcc_id[0]);
+            const CuId cu{w0.xcc, w0.se, w0.sh, w0.cu};
+            for (int w = 1; w < ldsmarch::kWaves; ++w) {
+                const SimdId id = decode_hw_id(r.hw_id[w], r.xcc_id[w]);
+                if (CuId{id.xcc, id.se, id.sh, id.cu} != cu) consistent = false;
+            }
+            ++blocks_of_cu[cu];
+            mismatches += r.mismatches;
+            if (r.mismatches) {
+                Bad &x = bad[cu];
+                x.mismatches += r.mismatches;
+                for (int w = 0; w < 4; ++w) x.bits[w] |= r.bad_bits[w];
+                if (r.first < x.first) {
+                    x.first = r.first;
+                    x.block = (uint32_t)b;
+                }
+            }
+        }
+        covered = (int)blocks_of_cu.size() >= cu_count;
+        if (blocks < cu_count) break;  // can never reach every CU
+    }
+
+    py::list bad_list;
+    for (const auto &kv : bad) {
+        const ldsmarch::First f = ldsmarch::unpack_first(kv.second.first);
+        const hbmmarch::Element p = hbmmarch::pattern(
+            (int)f.pattern, seed,
+            ldsmarch::pattern_index((int)f.path, kv.second.block, elems, f.element));
+        py::dict b;
+        b["xcc"] = std::get<0>(kv.first);
+        b["se"] = std::get<1>(kv.first);
+        b["sh"] = std::get<2>(kv.first);
+        b["cu"] = std::get<3>(kv.first);
+        b["mismatches"] = kv.second.mismatches;
+        b["bad_bits"] = py::make_tuple(kv.second.bits[0], kv.second.bits[1],
+                                       kv.second.bits[2], kv.second.bits[3]);
+        uint32_t expected = ldsmarch::word_of(
+            ldsmarch::expected_of((int)f.path, p, (int)f.step), f.word);
+        // tr16 reports one 16-bit value, at its place in the word
+        if (f.path == ldsmarch::kTr16)
+            expected &= f.half ? 0xFFFF0000u : 0x0000FFFFu;
+        b["first"] = lds_first_failure(f, expected);
+        bad_list.append(b);
+    }
+    // a CU that no wave ran on has no id to report: a count
+    const int uncovered = std::max(0, cu_count - (int)blocks_of_cu.size());
+
+    py::dict path_bytes, path_patterns;
+    for (int p = 0; p < ldsmarch::kPaths; ++p) {
+        if (!path_on[p]) continue;
+        path_bytes[ldsmarch::kPathNames[p]] =
+            ldsmarch::covered_bytes(p, (uint32_t)lds_bytes);
+        py::list names;
+        for (int q = 0; q < hbmmarch::kPatterns; ++q)
+            if (mask_of[p] >> q & 1) names.append(hbmmarch::kPatternNames[q]);
+        path_patterns[ldsmarch::kPathNames[p]] = names;
+    }
+
+    py::dict out;
+    out["cu_count"] = cu_count;
+    out["cus_covered"] = (int)blocks_of_cu.size();
+    out["coverage_complete"] = covered && consistent &&
+                               (int)blocks_of_cu.size() == cu_count &&
+                               lds_bytes == lds_bytes_per_cu;
+    out["placement_consistent"] = consistent;
+    out["uncovered"] = uncovered;
+    out["launches"] = launches;
+    out["reps"] = reps;  // of the last launch
+    out["blocks"] = blocks;
+    out["lds_bytes"] = lds_bytes;
+    out["lds_bytes_per_cu"] = lds_bytes_per_cu;
+    out["paths"] = path_bytes;
+    out["patterns"] = path_patterns;
+    out["seed"] = seed;
+    out["mismatches"] = mismatches;
+    out["bad"] = bad_list;
+    out["records"] = records;
+    out["sweep_ms"] = sweep_ms;
+    out["ok"] = mismatches == 0;
+    return out;
+}
+
+// The sweep's schedule for the tests: no HIP call, works without a GPU.
+py::dict lds_sweep_reference(long long lds_bytes) {
+    if (lds_bytes < 16 || lds_bytes % 16 ||
+        lds_bytes > (long long)ldsmarch::kMaxLdsBytes)
+        throw std::invalid_argument("lds_bytes must be a multiple of 16 in 16..2^22");
+    py::list paths;
+    for (int p = 0; p < ldsmarch::kPaths; ++p) {
+        py::dict d;
+        d["name"] = ldsmarch::kPathNames[p];
+        d["access_bytes"] = ldsmarch::access_bytes(p);
+        d["steps"] = ldsmarch::path_steps(p);
+        d["bytes"] = ldsmarch::covered_bytes(p, (uint32_t)lds_bytes);
+        d["accesses"] = ldsmarch::accesses(p, (uint32_t)lds_bytes);
+        py::list names, after;
+        for (int q = 0; q < hbmmarch::kPatterns; ++q)
+            if (ldsmarch::default_patterns(p) >> q & 1)
+                names.append(hbmmarch::kPatternNames[q]);
+        for (int s = 0; s < ldsmarch::path_steps(p); ++s)
+            if (ldsmarch::step_is_followed_by_read(p, s)) after.append(s);
+        d["default_patterns"] = names;
+        d["corruptible_after"] = after;
+        // [steps][items]: the thread that handles work item j in step s
+        py::list threads;
+        const uint32_t n = ldsmarch::accesses(p, (uint32_t)lds_bytes);
+        for (int s = 0; s < ldsmarch::path_steps(p); ++s) {
+            py::list row;
+            for (uint32_t j = 0; j < n; ++j)
+                row.append(ldsmarch::thread_of_item(p, s, n, j));
+            threads.append(row);
+        }
+        d["thread_of_item"] = threads;
+        paths.append(d);
+    }
+    py::list tr16;  // [256 threads][4]
+    for (uint32_t t = 0; t < (uint32_t)ldsmarch::kThreads; ++t) {
+        py::list row;
+        for (uint32_t q = 0; q < 4; ++q) row.append(ldsmarch::tr16_source(t, q));
+        tr16.append(row);
+    }
+    py::dict out;
+    out["paths"] = paths;
+    out["default_reps"] = ldsmarch::kDefaultReps;
+    out["threads"] = ldsmarch::kThreads;
+    out["tr16_source"] = tr16;
+    out["tr16_round_bytes"] = ldsmarch::kTr16Bytes;
+    out["dma_instruction_bytes"] = ldsmarch::kDmaBytes;
+    out["poison_byte"] = hbmpattern::kPoisonByte;
+    return out;
+}
+
 // (free, total) bytes of device memory, hipMemGetInfo.
 py::tuple mem_info(int device) {
     HIP_CHECK(hipSetDevice(device));
@@ -1185,5 +1580,10 @@ PYBIND11_MODULE(_healthprobe, m) {
           py::arg("max_records") = 64, py::arg("return_data") = false);
     m.def("hbm_march_reference", &hbm_march_reference, py::arg("pattern"),
           py::arg("seed"), py::arg("step"), py::arg("start"), py::arg("count"));
+    m.def("lds_sweep", &lds_sweep, py::arg("device") = 0,
+          py::arg("lds_bytes") = 0, py::arg("blocks") = 0, py::arg("reps") = 0,
+          py::arg("paths") = py::none(), py::arg("patterns") = py::none(),
+          py::arg("seed") = 0x5EEDull, py::arg("corrupt") = py::none());
+    m.def("lds_sweep_reference", &lds_sweep_reference, py::arg("lds_bytes"));
     m.def("mem_info", &mem_info, py::arg("device") = 0);
 }

@@ -9,6 +9,7 @@
 
 #include "hbm_march.h"
 #include "hbm_pattern.h"
+#include "lds_march.h"
 #include "sweep_table.h"
 
 namespace {  // one translation unit per binary; keep the kernels internal
@@ -536,6 +537,306 @@ cu_sweep_kernel(const uint4 *__restrict__ table, SweepRecord *records, int reps,
         rec->fail_pipes = st.fail_pipes;
         rec->bad_lanes_lo = (uint32_t)st.bad_lanes;
         rec->bad_lanes_hi = (uint32_t)(st.bad_lanes >> 32);
+    }
+}
+
+// ---------------- LDS sweep: march over one CU's whole LDS ----------------
+
+// A few of a block's bad accesses, each in a claimed slot.
+struct LdsSlot {
+    uint32_t meta;  // path | pattern << 4 | step << 8 | word << 12
+    uint32_t element;
+    uint32_t got, expected;  // the lowest differing word
+};
+constexpr int kLdsSlots = 4;
+
+// One record per block; the host zeroes the array and sets first = ~0
+// before the launch.
+struct LdsBlockRecord {
+    uint32_t hw_id[4], xcc_id[4];  // per wave: HW_REG_HW_ID, HW_REG_XCC_ID
+    uint32_t mismatches;           // accesses that read back wrong
+    uint32_t n_slots;              // slots claimed, may pass kLdsSlots
+    uint32_t bad_bits[4];          // OR of got ^ expected, per word
+    unsigned long long first;      // ldsmarch::pack_first of the lowest element
+    LdsSlot slots[kLdsSlots];
+};
+
+enum LdsCorruption { kLdsNone = 0, kLdsFlip = 1, kLdsAlias = 2 };
+
+struct LdsSweepParams {
+    uint32_t lds_bytes;  // a multiple of 16
+    int reps;
+    uint32_t patterns[ldsmarch::kPaths];  // bit p: pattern p runs; 0: path off
+    unsigned long long seed;
+    const u32x4 *image;  // the dma path's source, covered_bytes(kDma) of it
+    // one corruption, in rep 0 (c_block = -1: none)
+    int c_block, c_path, c_pattern, c_step, c_kind;
+    uint32_t c_element, c_word, c_bit;
+    int c_distance;
+};
+
+using u32x2 = __attribute__((ext_vector_type(2))) uint32_t;
+using i16x4 = __attribute__((ext_vector_type(4))) short;
+
+// The cold path: one access read back wrong.  got and want hold the
+// access's words at their place in the 16-byte element, zero elsewhere;
+// more is ORed into the bad bits of the lowest differing word (tr16: the
+// other 16-bit values of the same read, from the same `half` of that word).
+__device__ __noinline__ void lds_report(LdsBlockRecord *rec, uint32_t path,
+                                        uint32_t pattern, uint32_t step,
+                                        uint32_t element, u32x4 got, u32x4 want,
+                                        uint32_t more, uint32_t half = 0) {
+    // no array indexed at run time: that would cost the kernel scratch memory
+    const uint32_t d0 = got.x ^ want.x, d1 = got.y ^ want.y,
+                   d2 = got.z ^ want.z, d3 = got.w ^ want.w;
+    const uint32_t word = d0 ? 0 : d1 ? 1 : d2 ? 2 : 3;
+    atomicAdd(&rec->mismatches, 1u);
+    if (d0 | (word == 0 ? more : 0)) atomicOr(&rec->bad_bits[0], d0 | (word == 0 ? more : 0));
+    if (d1 | (word == 1 ? more : 0)) atomicOr(&rec->bad_bits[1], d1 | (word == 1 ? more : 0));
+    if (d2 | (word == 2 ? more : 0)) atomicOr(&rec->bad_bits[2], d2 | (word == 2 ? more : 0));
+    if (d3 | (word == 3 ? more : 0)) atomicOr(&rec->bad_bits[3], d3 | (word == 3 ? more : 0));
+    const uint32_t got_word = d0 ? got.x : d1 ? got.y : d2 ? got.z : got.w;
+    const uint32_t want_word = d0 ? want.x : d1 ? want.y : d2 ? want.z : want.w;
+    atomicMin(&rec->first, (unsigned long long)ldsmarch::pack_first(
+                               element, path, pattern, step, word, half, got_word));
+    // the plain read keeps a wholly bad block from wrapping the counter
+    if (*(volatile uint32_t *)&rec->n_slots < (uint32_t)kLdsSlots) {
+        const uint32_t slot = atomicAdd(&rec->n_slots, 1u);
+        if (slot < (uint32_t)kLdsSlots) {
+            LdsSlot s;
+            s.meta = path | pattern << 4 | step << 8 | word << 12;
+            s.element = element;
+            s.got = got_word;
+            s.expected = want_word;
+            rec->slots[slot] = s;
+        }
+    }
+}
+
+// Thread 0 of the chosen block damages its own block's LDS once, after
+// step `step` of that path and pattern in rep 0; the caller's barrier has
+// passed and a second one follows, on a block-uniform condition.
+__device__ inline void lds_corrupt(u32x4 *lds, const LdsSweepParams &a, int rep,
+                                   int path, int pattern, int step) {
+    if (rep == 0 && (int)blockIdx.x == a.c_block && path == a.c_path &&
+        pattern == a.c_pattern && step == a.c_step) {
+        const uint32_t elems = a.lds_bytes / 16;
+        const long long other = (long long)a.c_element + a.c_distance;
+        if (threadIdx.x == 0 && a.c_element < elems) {
+            if (a.c_kind == kLdsFlip && a.c_word < 4)
+                reinterpret_cast<uint32_t *>(lds)[a.c_element * 4 + a.c_word] ^=
+                    1u << (a.c_bit & 31);
+            else if (a.c_kind == kLdsAlias && other >= 0 && other < (long long)elems)
+                lds[a.c_element] = lds[other];
+        }
+        __syncthreads();
+    }
+}
+
+// The four march steps of one pattern at one access width (ldsmarch::kB128,
+// kB64, kB32).  In step s thread t handles the accesses
+// lane_residue(s, t) + 256 k, from the top in the descending step; a step
+// writes the complement of what it EXPECTED.
+template <int PATH>
+__device__ inline void lds_march(u32x4 *lds, const LdsSweepParams &a, int rep,
+                                 int pattern, LdsBlockRecord *rec) {
+    constexpr uint32_t W = ldsmarch::access_bytes(PATH);
+    const uint32_t n = a.lds_bytes / W, elems = a.lds_bytes / 16;
+    const unsigned long long base = (unsigned long long)blockIdx.x * elems;
+    for (int step = 0; step < hbmmarch::kSteps; ++step) {
+        const uint32_t r = ldsmarch::lane_residue(step, threadIdx.x);
+        const uint32_t count = n > r ? (n - r + ldsmarch::kThreads - 1) / ldsmarch::kThreads : 0;
+        const bool reads = hbmmarch::step_reads(step), writes = hbmmarch::step_writes(step);
+        for (uint32_t k = 0; k < count; ++k) {
+            const uint32_t acc =
+                r + ldsmarch::kThreads * (hbmmarch::step_descends(step) ? count - 1 - k : k);
+            const uint32_t e = acc * W / 16;
+            const hbmmarch::Element p = hbmmarch::pattern(pattern, a.seed, base + e);
+            const hbmmarch::Element v = hbmmarch::expected_of(p, step);
+            const hbmmarch::Element x = hbmmarch::to_write_of(p, step);
+            if constexpr (PATH == ldsmarch::kB128) {
+                if (reads) {
+                    const u32x4 got = lds[acc];
+                    const u32x4 want = {v.w[0], v.w[1], v.w[2], v.w[3]};
+                    if ((got.x ^ want.x) | (got.y ^ want.y) | (got.z ^ want.z) |
+                        (got.w ^ want.w))
+                        lds_report(rec, PATH, pattern, step, e, got, want, 0);
+                }
+                if (writes) lds[acc] = u32x4{x.w[0], x.w[1], x.w[2], x.w[3]};
+            } else if constexpr (PATH == ldsmarch::kB64) {
+                u32x2 *l2 = reinterpret_cast<u32x2 *>(lds);
+                const bool hi = acc & 1;
+                if (reads) {
+                    const u32x2 got = l2[acc];
+                    const u32x2 want = {hi ? v.w[2] : v.w[0], hi ? v.w[3] : v.w[1]};
+                    if ((got.x ^ want.x) | (got.y ^ want.y)) {
+                        const u32x4 g = hi ? u32x4{0, 0, got.x, got.y} : u32x4{got.x, got.y, 0, 0};
+                        const u32x4 w = hi ? u32x4{0, 0, want.x, want.y} : u32x4{want.x, want.y, 0, 0};
+                        lds_report(rec, PATH, pattern, step, e, g, w, 0);
+                    }
+                }
+                if (writes) l2[acc] = u32x2{hi ? x.w[2] : x.w[0], hi ? x.w[3] : x.w[1]};
+            } else {
+                static_assert(PATH == ldsmarch::kB32, "three widths");
+                uint32_t *l1 = reinterpret_cast<uint32_t *>(lds);
+                const uint32_t word = acc & 3;
+                if (reads) {
+                    const uint32_t got = l1[acc], want = ldsmarch::word_of(v, word);
+                    if (got != want) {
+                        const u32x4 g = {word == 0 ? got : 0, word == 1 ? got : 0,
+                                         word == 2 ? got : 0, word == 3 ? got : 0};
+                        const u32x4 w = {word == 0 ? want : 0, word == 1 ? want : 0,
+                                         word == 2 ? want : 0, word == 3 ? want : 0};
+                        lds_report(rec, PATH, pattern, step, e, g, w, 0);
+                    }
+                }
+                if (writes) l1[acc] = ldsmarch::word_of(x, word);
+            }
+        }
+        __syncthreads();
+        lds_corrupt(lds, a, rep, PATH, pattern, step);
+    }
+}
+
+// Every element of the block's LDS := `poison` or pattern p, 16-byte stores,
+// thread t the elements t + 256 k (step 0 of dma and of tr16).
+__device__ inline void lds_fill(u32x4 *lds, const LdsSweepParams &a, int path,
+                                int pattern) {
+    const uint32_t elems = a.lds_bytes / 16;
+    for (uint32_t e = threadIdx.x; e < elems; e += ldsmarch::kThreads) {
+        const hbmmarch::Element x = ldsmarch::to_write_of(
+            path, hbmmarch::pattern(pattern, a.seed,
+                                    ldsmarch::pattern_index(path, blockIdx.x, elems, e)),
+            0);
+        lds[e] = u32x4{x.w[0], x.w[1], x.w[2], x.w[3]};
+    }
+    __syncthreads();
+}
+
+// dma: poison, fill every whole KiB from the global image with LDS-DMA
+// (wave w's instruction k: KiB 4k + w, a wave-uniform LDS base to which the
+// hardware adds lane * 16), read-verify with 16-byte loads by the waves two
+// further on.  A byte the fill did not reach still holds the poison and is
+// a counted mismatch.
+__device__ inline void lds_dma(u32x4 *lds, const LdsSweepParams &a, int rep,
+                               LdsBlockRecord *rec) {
+#if defined(__gfx950__)
+    constexpr int P = hbmmarch::kRandom;
+    lds_fill(lds, a, ldsmarch::kDma, P);
+    lds_corrupt(lds, a, rep, ldsmarch::kDma, P, 0);
+
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t instructions = ldsmarch::dma_instructions(a.lds_bytes, wave);
+    for (uint32_t k = 0; k < instructions; ++k) {
+        const uint32_t kib = __builtin_amdgcn_readfirstlane(ldsmarch::dma_kib(wave, k));
+        __builtin_amdgcn_global_load_lds(
+            (const __attribute__((address_space(1))) void *)(a.image + 64 * kib + lane),
+            (__attribute__((address_space(3))) void *)(reinterpret_cast<char *>(lds) +
+                                                       ldsmarch::kDmaBytes * kib),
+            16, 0, 0);
+    }
+    __syncthreads();  // waits for vmcnt(0) first: the fill has landed
+    lds_corrupt(lds, a, rep, ldsmarch::kDma, P, 1);
+
+    const uint32_t n = ldsmarch::accesses(ldsmarch::kDma, a.lds_bytes);
+    for (uint32_t e = ldsmarch::lane_residue(2, threadIdx.x); e < n; e += ldsmarch::kThreads) {
+        const hbmmarch::Element v = hbmmarch::pattern(P, a.seed, e);
+        const u32x4 got = lds[e];
+        const u32x4 want = {v.w[0], v.w[1], v.w[2], v.w[3]};
+        if ((got.x ^ want.x) | (got.y ^ want.y) | (got.z ^ want.z) | (got.w ^ want.w))
+            lds_report(rec, ldsmarch::kDma, P, 2, e, got, want, 0);
+    }
+    __syncthreads();
+#else
+    (void)lds;
+    (void)a;
+    (void)rep;
+    (void)rec;
+#endif
+}
+
+// tr16: write the address pattern, then ds_read_b64_tr_b16 over every whole
+// 2048 bytes: thread t of round k gives the address 2048 k + 8 t, and its
+// four 16-bit results must come from ldsmarch::tr16_source(t, 0..3).  The
+// trip count is uniform and every address in bounds, so EXEC is all ones at
+// the read; the only lane-dependent branch is the report after it.
+__device__ inline void lds_tr16(u32x4 *lds, const LdsSweepParams &a, int rep,
+                                LdsBlockRecord *rec) {
+#if defined(__gfx950__)
+    constexpr int P = hbmmarch::kAddress;
+    lds_fill(lds, a, ldsmarch::kTr16, P);
+    lds_corrupt(lds, a, rep, ldsmarch::kTr16, P, 0);
+
+    const uint32_t elems = a.lds_bytes / 16, t = threadIdx.x;
+    const unsigned long long base = (unsigned long long)blockIdx.x * elems;
+    const uint32_t rounds = ldsmarch::tr16_rounds(a.lds_bytes);
+    // the same for q = 0..3: 32 q is a multiple of 16
+    const uint32_t byte = ldsmarch::tr16_source(t, 0) % 16, shift = 8 * (byte % 4);
+    for (uint32_t k = 0; k < rounds; ++k) {
+        const i16x4 got = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+            (__attribute__((address_space(3))) i16x4 *)(reinterpret_cast<char *>(lds) +
+                                                        ldsmarch::tr16_address(t, k)));
+        const uint32_t first_e = (ldsmarch::kTr16Bytes * k + ldsmarch::tr16_source(t, 0)) / 16;
+        // element q's source: two elements on per q (32 bytes)
+        const uint32_t g0 = (uint16_t)got.x, g1 = (uint16_t)got.y,
+                       g2 = (uint16_t)got.z, g3 = (uint16_t)got.w;
+        const uint32_t w0 = ldsmarch::half_of(hbmmarch::pattern(P, a.seed, base + first_e), byte),
+                       w1 = ldsmarch::half_of(hbmmarch::pattern(P, a.seed, base + first_e + 2), byte),
+                       w2 = ldsmarch::half_of(hbmmarch::pattern(P, a.seed, base + first_e + 4), byte),
+                       w3 = ldsmarch::half_of(hbmmarch::pattern(P, a.seed, base + first_e + 6), byte);
+        const uint32_t d0 = g0 ^ w0, d1 = g1 ^ w1, d2 = g2 ^ w2, d3 = g3 ^ w3;
+        if (d0 | d1 | d2 | d3) {
+            const uint32_t q = d0 ? 0 : d1 ? 1 : d2 ? 2 : 3;
+            const uint32_t g = (d0 ? g0 : d1 ? g1 : d2 ? g2 : g3) << shift;
+            const uint32_t w = (d0 ? w0 : d1 ? w1 : d2 ? w2 : w3) << shift;
+            const uint32_t word = byte / 4;
+            const u32x4 gv = {word == 0 ? g : 0, word == 1 ? g : 0,
+                              word == 2 ? g : 0, word == 3 ? g : 0};
+            const u32x4 wv = {word == 0 ? w : 0, word == 1 ? w : 0,
+                              word == 2 ? w : 0, word == 3 ? w : 0};
+            lds_report(rec, ldsmarch::kTr16, P, 1, first_e + 2 * q, gv, wv,
+                       (d0 | d1 | d2 | d3) << shift, byte % 4 / 2);
+        }
+    }
+    __syncthreads();
+#else
+    (void)lds;
+    (void)a;
+    (void)rep;
+    (void)rec;
+#endif
+}
+
+template <int PATH>
+__device__ inline void lds_march_patterns(u32x4 *lds, const LdsSweepParams &a,
+                                          int rep, LdsBlockRecord *rec) {
+    for (int p = 0; p < hbmmarch::kPatterns; ++p)
+        if (a.patterns[PATH] >> p & 1) lds_march<PATH>(lds, a, rep, p, rec);
+}
+
+// One 4-wave block with a.lds_bytes of dynamic LDS: at the card's
+// sharedMemPerBlock that is a CU's whole LDS, so no two such blocks share a
+// CU.  Each wave records where it runs; the block then runs a.reps rounds
+// of the selected paths and patterns (lds_march.h) over its LDS and reports
+// into its own record.  Nothing depends on where a block lands and no block
+// waits for another; the host works out the coverage from the records.
+// Every LDS address is below a.lds_bytes for every multiple of 16.
+__global__ void __launch_bounds__(256)
+lds_sweep_kernel(LdsSweepParams a, LdsBlockRecord *records) {
+    extern __shared__ u32x4 lds_sweep_mem[];
+    u32x4 *lds = lds_sweep_mem;
+    LdsBlockRecord *rec = &records[blockIdx.x];
+    if ((threadIdx.x & 63) == 0) {
+        rec->hw_id[threadIdx.x >> 6] = __builtin_amdgcn_s_getreg(4 | 31 << 11);
+        rec->xcc_id[threadIdx.x >> 6] = __builtin_amdgcn_s_getreg(20 | 3 << 11);
+    }
+    for (int rep = 0; rep < a.reps; ++rep) {
+        lds_march_patterns<ldsmarch::kB128>(lds, a, rep, rec);
+        lds_march_patterns<ldsmarch::kB64>(lds, a, rep, rec);
+        lds_march_patterns<ldsmarch::kB32>(lds, a, rep, rec);
+        if (a.patterns[ldsmarch::kDma]) lds_dma(lds, a, rep, rec);
+        if (a.patterns[ldsmarch::kTr16]) lds_tr16(lds, a, rep, rec);
     }
 }
 

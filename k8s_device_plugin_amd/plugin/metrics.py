@@ -71,6 +71,17 @@ class _ManagerCollector:
                           sum(inst.plugin._sweep_bad_simds.values()))
         yield bs
 
+        bl = GaugeMetricFamily(
+            "amdgpu_dp_deep_probe_bad_lds_cus",
+            "CUs whose LDS failed the last deep-probe LDS sweep, summed over "
+            "GPUs (0 while the sweep is off)",
+            labels=["resource"],
+        )
+        for resource, inst in self.manager.plugins.items():
+            bl.add_metric([resource],
+                          sum(inst.plugin._sweep_bad_lds_cus.values()))
+        yield bl
+
         counters = {}
         for resource, inst in self.manager.plugins.items():
             if inst.native:

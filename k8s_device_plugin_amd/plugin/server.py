@@ -60,6 +60,7 @@ class AMDGPUPlugin:
         deep_probe_every: int = 0,
         dev_root: str = "/dev",
         deep_cu_sweep: bool = False,
+        deep_lds_sweep: bool = False,
     ):
         self.resource = resource
         self.cdi_enabled = cdi_enabled
@@ -85,6 +86,10 @@ class AMDGPUPlugin:
         # its own, so all XCDs are covered)
         self.deep_cu_sweep = deep_cu_sweep
         self._sweep_bad_simds: Dict[str, int] = {}  # dev_id -> last count
+        # likewise the march test of every CU's whole LDS (LDS sweep), on
+        # every ordinal; independent of the CU sweep
+        self.deep_lds_sweep = deep_lds_sweep
+        self._sweep_bad_lds_cus: Dict[str, int] = {}  # dev_id -> last count
         self.dev_root = dev_root
         self.paths = paths
         self.devices: Dict[str, GPUDevice] = {}
@@ -206,41 +211,67 @@ class AMDGPUPlugin:
 
     def _deep_probe(self, dev: GPUDevice) -> dict:
         """The deep probe of one physical GPU: MFMA/LDS/HBM with floors on
-        its first HIP ordinal and, with deep_cu_sweep, the CU sweep on
-        every ordinal, its bad-SIMD lines merged into floor_violations."""
+        its first HIP ordinal and, with deep_cu_sweep and / or
+        deep_lds_sweep, that sweep on every ordinal, its bad-SIMD or bad-CU
+        lines merged into floor_violations."""
         from ..native import (
             cu_sweep_violations,
             deep_health_probe,
+            lds_sweep_with_ecc,
             run_cu_sweep,
         )
 
         # hbm_scrub_bytes=0: never the HBM scrub here, whatever
-        # AMDXDP_HBM_SCRUB_BYTES says; on a live node the pods own the VRAM
-        if not self.deep_cu_sweep:
-            return deep_health_probe(device=self._hip_ordinal(dev),
-                                     hbm_scrub_bytes=0)
+        # AMDXDP_HBM_SCRUB_BYTES says; on a live node the pods own the VRAM.
+        # A sweep that its flag turns on runs below, on every ordinal, so it
+        # is off in the probe itself; one whose flag is off is left to the
+        # environment, as before there were flags.
         ordinals = self._hip_ordinals(dev)
-        res = deep_health_probe(device=ordinals[0], cu_sweep=False,
-                                hbm_scrub_bytes=0)
-        res["cu_sweep"] = {}
-        bad_simds = 0
-        for ordinal in ordinals:
-            sweep = run_cu_sweep(ordinal)
-            res["cu_sweep"][ordinal] = sweep
-            bad_simds += len(sweep.get("bad", []))
-            for line in cu_sweep_violations(sweep):
-                line = f"{line} (hip device {ordinal})"
-                log.error("deep probe on %s: %s", dev.dev_id, line)
-                res["floor_violations"].append(line)
-            if sweep.get("ok") and not sweep.get("coverage_complete"):
-                log.warning(
-                    "deep probe on %s: cu_sweep reached %s of %s CUs on hip "
-                    "device %d", dev.dev_id, sweep.get("cus_covered"),
-                    sweep.get("cu_count"), ordinal,
-                )
-        self._sweep_bad_simds[dev.dev_id] = bad_simds
-        if bad_simds:
-            res["healthy"] = False
+        sweeps = {}
+        if self.deep_cu_sweep:
+            sweeps["cu_sweep"] = False
+        if self.deep_lds_sweep:
+            sweeps["lds_sweep"] = False
+        res = deep_health_probe(device=ordinals[0], hbm_scrub_bytes=0, **sweeps)
+        if self.deep_cu_sweep:
+            res["cu_sweep"] = {}
+            bad_simds = 0
+            for ordinal in ordinals:
+                sweep = run_cu_sweep(ordinal)
+                res["cu_sweep"][ordinal] = sweep
+                bad_simds += len(sweep.get("bad", []))
+                for line in cu_sweep_violations(sweep):
+                    line = f"{line} (hip device {ordinal})"
+                    log.error("deep probe on %s: %s", dev.dev_id, line)
+                    res["floor_violations"].append(line)
+                if sweep.get("ok") and not sweep.get("coverage_complete"):
+                    log.warning(
+                        "deep probe on %s: cu_sweep reached %s of %s CUs on "
+                        "hip device %d", dev.dev_id, sweep.get("cus_covered"),
+                        sweep.get("cu_count"), ordinal,
+                    )
+            self._sweep_bad_simds[dev.dev_id] = bad_simds
+            if bad_simds:
+                res["healthy"] = False
+        if self.deep_lds_sweep:
+            res["lds_sweep"] = {}
+            bad_cus = 0
+            unhealthy = False
+            for ordinal in ordinals:
+                sweep = lds_sweep_with_ecc(ordinal)
+                res["lds_sweep"][ordinal] = sweep
+                bad_cus += len(sweep.get("bad", []))
+                for line in sweep["violations"]:
+                    line = f"{line} (hip device {ordinal})"
+                    log.error("deep probe on %s: %s", dev.dev_id, line)
+                    res["floor_violations"].append(line)
+                    unhealthy = True
+                for line in sweep["warnings"]:
+                    log.warning("deep probe on %s: %s (hip device %d)",
+                                dev.dev_id, line, ordinal)
+            self._sweep_bad_lds_cus[dev.dev_id] = bad_cus
+            if unhealthy:
+                res["healthy"] = False
         return res
 
     def _run_deep_check(self) -> None:
