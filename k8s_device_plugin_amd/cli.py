@@ -69,6 +69,12 @@ def device_plugin_main(argv=None) -> int:
                          "run exact known-answer matrix products on every "
                          "SIMD of every CU, on every HIP device of the GPU, "
                          "and pin a GPU with a bad SIMD Unhealthy")
+    ap.add_argument("--deep-probe-cu-sweep-extra", default="",
+                    metavar="mx,wide|all",
+                    help="with --deep-probe-cu-sweep: sweep these extra pipe "
+                         "sets too, wherever the base sweep runs: mx "
+                         "(block-scaled fp4 / fp6 with live scales), wide "
+                         "(bf8, 32x32 f16 / fp8 / i8, f64, f32-input)")
     ap.add_argument("--deep-probe-lds-sweep", action="store_true",
                     help="with --deep-probe-every / --prestart-deep: also "
                          "march-test the whole LDS of every CU through every "
@@ -90,6 +96,14 @@ def device_plugin_main(argv=None) -> int:
                          "behavior); default is in-process re-registration")
     ap.add_argument("-v", "--verbose", action="count", default=0)
     args = ap.parse_args(argv)
+    from .native import cu_sweep_extra_sets
+
+    try:
+        sweep_extra = cu_sweep_extra_sets(args.deep_probe_cu_sweep_extra)
+    except ValueError as e:
+        ap.error(f"--deep-probe-cu-sweep-extra: {e}")
+    if sweep_extra and not args.deep_probe_cu_sweep:
+        ap.error("--deep-probe-cu-sweep-extra requires --deep-probe-cu-sweep")
     _setup_logging(args.verbose)
     log = logging.getLogger("amd-device-plugin")
     # startup banner (reference: main.go:94-121 logs name+version lines)
@@ -203,6 +217,7 @@ def device_plugin_main(argv=None) -> int:
                                  prestart_deep=args.prestart_deep,
                                  deep_probe_every=args.deep_probe_every,
                                  deep_cu_sweep=args.deep_probe_cu_sweep,
+                                 deep_cu_sweep_extra=sweep_extra,
                                  deep_lds_sweep=args.deep_probe_lds_sweep,
                                  exit_on_stream_loss=args.exit_on_stream_loss),
         device_plugin_path=args.kubelet_dir or dp.DEVICE_PLUGIN_PATH,

@@ -106,19 +106,65 @@ def cu_sweep_enabled(cu_sweep: Optional[bool] = None) -> bool:
     return os.environ.get(CU_SWEEP_ENV, "0").strip() not in ("", "0")
 
 
-def _sweep_inject_from_env():
-    """AMDXDP_CU_SWEEP_INJECT="block:wave:pipe" -> (block, wave, pipe): the
-    sweep then simulates one bad matrix pipe on healthy hardware."""
+CU_SWEEP_EXTRA_ENV = "AMDXDP_CU_SWEEP_EXTRA"
+# The pipes of each set, in the order of native/sweep_table.h and
+# native/sweep_table_ext.h: an injection by name finds its set and index here.
+CU_SWEEP_PIPES = {
+    "base": ("bf16_16", "bf16_32", "f16_16", "fp8_16", "i8_16", "mxfp8_16"),
+    "mx": ("mxfp4_16", "mxfp4_32", "mxfp6_16", "mxbf6_16", "mxfp8xfp4_16"),
+    "wide": ("bf8_16", "f16_32", "fp8_32", "i8_32", "f64_16", "f32_16"),
+}
+CU_SWEEP_EXTRA_SETS = ("mx", "wide")
+
+
+def cu_sweep_extra_sets(cu_sweep_extra=None) -> tuple:
+    """The extra pipe sets to sweep, in the order mx, wide.  An explicit
+    argument wins: "all", a comma list or an iterable of set names; None
+    reads AMDXDP_CU_SWEEP_EXTRA (unset or empty = none)."""
+    spec = cu_sweep_extra
+    if spec is None:
+        spec = os.environ.get(CU_SWEEP_EXTRA_ENV, "")
+    if isinstance(spec, str):
+        spec = [s.strip() for s in spec.split(",") if s.strip()]
+    names = [str(s).strip().lower() for s in spec]
+    if "all" in names:
+        if len(names) != 1:
+            raise ValueError("cu_sweep_extra: all stands alone")
+        return CU_SWEEP_EXTRA_SETS
+    for name in names:
+        if name not in CU_SWEEP_EXTRA_SETS:
+            raise ValueError(
+                f"cu_sweep_extra: unknown pipe set {name!r}, expected all or "
+                "some of " + ", ".join(CU_SWEEP_EXTRA_SETS))
+    return tuple(s for s in CU_SWEEP_EXTRA_SETS if s in names)
+
+
+def _sweep_inject_from_env(pipe_set: str = "base"):
+    """AMDXDP_CU_SWEEP_INJECT="block:wave:pipe" -> (block, wave, pipe) for
+    the set that owns the pipe, None for every other set: the sweep then
+    simulates one bad matrix pipe on healthy hardware.  pipe is an index
+    into the base set or the name of a pipe of any set."""
     spec = os.environ.get(CU_SWEEP_INJECT_ENV, "").strip()
     if not spec:
         return None
+    fields = spec.split(":")
     try:
-        block, wave, pipe = (int(x) for x in spec.split(":"))
-    except ValueError:
+        block, wave = (int(x) for x in fields[:2])
+        if len(fields) != 3:
+            raise ValueError
+        try:
+            owner, pipe = "base", int(fields[2])
+        except ValueError:
+            name = fields[2].strip()
+            owner = next(s for s, pipes in CU_SWEEP_PIPES.items()
+                         if name in pipes)
+            pipe = CU_SWEEP_PIPES[owner].index(name)
+    except (ValueError, StopIteration):
         raise ValueError(
-            f"{CU_SWEEP_INJECT_ENV}={spec!r}: expected block:wave:pipe"
+            f"{CU_SWEEP_INJECT_ENV}={spec!r}: expected block:wave:pipe, pipe "
+            "an index into the base set or a pipe's name"
         ) from None
-    return (block, wave, pipe)
+    return (block, wave, pipe) if owner == pipe_set else None
 
 
 def cu_sweep_violations(sweep: dict) -> list:
@@ -132,11 +178,26 @@ def cu_sweep_violations(sweep: dict) -> list:
     ]
 
 
-def run_cu_sweep(device: int = 0, mod=None) -> dict:
-    """Known-answer MFMA sweep of every CU and SIMD of one HIP device."""
+def run_cu_sweep(device: int = 0, mod=None, pipe_set: str = "base") -> dict:
+    """Known-answer MFMA sweep of every CU and SIMD of one HIP device, over
+    the base pipes or one of the extra sets (CU_SWEEP_EXTRA_SETS)."""
     if mod is None:
         mod = load_healthprobe(required=True)
-    return mod.cu_sweep(device=device, inject=_sweep_inject_from_env())
+    inject = _sweep_inject_from_env(pipe_set)
+    if pipe_set == "base":
+        return mod.cu_sweep(device=device, inject=inject)
+    return mod.cu_sweep(device=device, inject=inject, pipe_set=pipe_set)
+
+
+def cu_sweep_incomplete_warning(sweep: dict, pipe_set: str = "base"):
+    """The warning line of a sweep that found nothing bad but could not reach
+    every SIMD, or None."""
+    if not sweep.get("ok") or sweep.get("coverage_complete"):
+        return None
+    tag = "" if pipe_set == "base" else f"[{pipe_set}]"
+    return "cu_sweep_incomplete{}: {} of {} CUs, {} SIMDs".format(
+        tag, sweep.get("cus_covered"), sweep.get("cu_count"),
+        sweep.get("simds_covered"))
 
 
 LDS_SWEEP_ENV = "AMDXDP_LDS_SWEEP"
@@ -358,6 +419,7 @@ def deep_health_probe(
     hbm_scrub_bytes=None,
     lds_sweep: Optional[bool] = None,
     sysroot: str = "/",
+    cu_sweep_extra=None,
 ) -> dict:
     """Run the on-GPU MFMA/LDS/HBM probe and apply performance floors.
 
@@ -369,6 +431,13 @@ def deep_health_probe(
     MFMA sweep of every CU and SIMD under `cu_sweep`: a bad SIMD makes the
     GPU unhealthy, with one violation line each; a sweep that could not reach
     every SIMD but found nothing bad only sets `warnings`.
+
+    cu_sweep_extra (None = env AMDXDP_CU_SWEEP_EXTRA, default none; "all" or
+    an iterable of "mx" / "wide") acts only while the CU sweep is on: the
+    same sweep over the block-scaled fp4 / fp6 pipes (mx) and over bf8, the
+    32x32 shapes, f64 and f32-input (wide), under `cu_sweep_extra` as
+    {set: dict}, with the same violation lines and a warning of its own for a
+    clean but incomplete set.
 
     hbm_scrub_bytes (None = env AMDXDP_HBM_SCRUB_BYTES, default off; "all" or
     a byte count) adds the march test of that much VRAM under `hbm_scrub`;
@@ -387,6 +456,8 @@ def deep_health_probe(
     if hbm_floor_gbps is None:
         hbm_floor_gbps = _floor_from_env(HBM_FLOOR_ENV,
                                          DEFAULT_HBM_FLOOR_GBPS)
+    if cu_sweep_extra is not None:
+        cu_sweep_extra = cu_sweep_extra_sets(cu_sweep_extra)  # or ValueError
     mod = load_healthprobe(required=True)
     res = mod.run_probe(device=device, hbm_bytes=hbm_bytes)
     violations = []
@@ -412,12 +483,16 @@ def deep_health_probe(
         sweep = run_cu_sweep(device, mod)
         res["cu_sweep"] = sweep
         violations.extend(cu_sweep_violations(sweep))
-        if sweep.get("ok") and not sweep.get("coverage_complete"):
-            res["warnings"] = [
-                "cu_sweep_incomplete: {} of {} CUs, {} SIMDs".format(
-                    sweep.get("cus_covered"), sweep.get("cu_count"),
-                    sweep.get("simds_covered"))
-            ]
+        warning = cu_sweep_incomplete_warning(sweep)
+        if warning:
+            res["warnings"] = [warning]
+        for pipe_set in cu_sweep_extra_sets(cu_sweep_extra):
+            sweep = run_cu_sweep(device, mod, pipe_set)
+            res.setdefault("cu_sweep_extra", {})[pipe_set] = sweep
+            violations.extend(cu_sweep_violations(sweep))
+            warning = cu_sweep_incomplete_warning(sweep, pipe_set)
+            if warning:
+                res.setdefault("warnings", []).append(warning)
     if lds_sweep_enabled(lds_sweep):
         sweep = lds_sweep_with_ecc(device, mod, sysroot)
         res["lds_sweep"] = sweep

@@ -56,8 +56,8 @@ def build_drmctl(force: bool = False) -> str:
 # headers shared by the probe and the sweeps
 _HIP_HEADERS = [os.path.join(PKG_DIR, h)
                 for h in ("hip_util.h", "probe_kernels.h",
-                          "sweep_table.h", "hbm_pattern.h", "hbm_march.h",
-                          "lds_march.h")]
+                          "sweep_table.h", "sweep_table_ext.h",
+                          "hbm_pattern.h", "hbm_march.h", "lds_march.h")]
 
 
 def build_healthprobe(force: bool = False) -> str:

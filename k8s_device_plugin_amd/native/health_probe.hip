@@ -12,7 +12,10 @@
 //      of the copy equals a pattern that does not repeat (hbm_pattern.h);
 //   5. on request (cu_sweep), exact known-answer products of the bf16, f16,
 //      fp8, i8 and MX-fp8 matrix pipes on every SIMD of every CU, with the
-//      place each wave ran read from the hardware id registers;
+//      place each wave ran read from the hardware id registers; with
+//      pipe_set "mx" / "wide" the same over block-scaled fp4 / fp6 with
+//      live scales and over bf8, the 32x32 shapes, f64 and f32-input
+//      (sweep_table_ext.h);
 //   6. on request (hbm_scrub), in-place march passes over all free VRAM:
 //      fused read-verify-write at streaming rate, four data patterns and
 //      their complements (hbm_march.h);
@@ -35,6 +38,7 @@
 #include <map>
 #include <string>
 #include <tuple>
+#include <utility>
 #include <vector>
 
 #include <pybind11/pybind11.h>
@@ -454,7 +458,22 @@ py::bytes mfma_peak_check(int device, int iters, int blocks) {
 // as long (53 us) and runs every product 8 times, for 1 % of the probe's
 // 5.5 ms.
 constexpr int kSweepDefaultReps = 8;
+// The same for the extra sets, chosen the same way from
+// profiles/cu_sweep_ext_mi355x.md: reps = 1 (mx 24 us, wide 25 us) reached
+// all 1024 SIMDs in one launch 24 of 24 times each, so coverage asks for no
+// more; 8 keeps a block alive 2.2x (mx, 52 us) and 2.5x (wide, 64 us) as
+// long and runs every product 8 times, each under 1 % of the plain probe's
+// 6.5 ms measured in the same session.  16 would double that again (85 and
+// 110 us) for nothing the coverage needs.
+constexpr int kSweepMxDefaultReps = 8;
+constexpr int kSweepWideDefaultReps = 8;
 constexpr int kSweepMaxLaunches = 4;
+
+constexpr int sweep_default_reps(int set) {
+    return set == cusweepx::kMx     ? kSweepMxDefaultReps
+           : set == cusweepx::kWide ? kSweepWideDefaultReps
+                                    : kSweepDefaultReps;
+}
 
 struct SimdId {
     int xcc, se, sh, cu, simd;
@@ -476,17 +495,24 @@ py::tuple decode_hw_id_py(uint32_t hw_id, uint32_t xcc_id) {
     return py::make_tuple(id.xcc, id.se, id.sh, id.cu, id.simd);
 }
 
-py::list sweep_pipe_names(uint32_t mask) {
+// "base", "mx" or "wide" -> cusweepx::Set
+int sweep_set_of(const std::string &name) {
+    for (int s = 0; s < cusweepx::kSets; ++s)
+        if (name == cusweepx::kSetName[s]) return s;
+    throw std::invalid_argument("pipe_set must be base, mx or wide, not " + name);
+}
+
+py::list sweep_pipe_names(int set, uint32_t mask) {
     py::list names;
-    for (int p = 0; p < cusweep::kPipes; ++p)
-        if (mask >> p & 1) names.append(cusweep::kPipeDesc[p].name);
+    for (int p = 0; p < cusweepx::n_pipes(set); ++p)
+        if (mask >> p & 1) names.append(cusweepx::pipe_name(set, p));
     return names;
 }
 
-py::dict sweep_first_failure(const SweepRecord &r) {
+py::dict sweep_first_failure(int set, const SweepRecord &r) {
     py::dict first;
-    first["pipe"] = r.first_pipe < (uint32_t)cusweep::kPipes
-                        ? cusweep::kPipeDesc[r.first_pipe].name : "?";
+    first["pipe"] = r.first_pipe < (uint32_t)cusweepx::n_pipes(set)
+                        ? cusweepx::pipe_name(set, (int)r.first_pipe) : "?";
     first["t"] = r.first_t;
     first["lane"] = r.first_lane;
     first["reg"] = r.first_reg;
@@ -499,8 +525,13 @@ py::dict sweep_first_failure(const SweepRecord &r) {
 // One launch of cu_count blocks; where the records show a SIMD that no wave
 // ran on, launch again with doubled reps (longer-lived blocks overlap more
 // surely), at most kSweepMaxLaunches in all, accumulating coverage and
-// failures.  inject = (block, wave, pipe) simulates one bad pipe.
-py::dict cu_sweep(int device, int reps, py::object inject) {
+// failures.  inject = (block, wave, pipe) simulates one bad pipe.  pipe_set
+// chooses the pipes: "base" (sweep_table.h), "mx" or "wide"
+// (sweep_table_ext.h); pipe indices and names are the set's own.
+py::dict cu_sweep(int device, int reps, py::object inject,
+                  const std::string &pipe_set) {
+    const int set = sweep_set_of(pipe_set);
+    const int n_pipes = cusweepx::n_pipes(set);
     int inj[3] = {-1, -1, -1};
     if (!inject.is_none()) {
         py::sequence seq = inject.cast<py::sequence>();
@@ -508,13 +539,13 @@ py::dict cu_sweep(int device, int reps, py::object inject) {
             throw std::invalid_argument("inject must be (block, wave, pipe)");
         for (int i = 0; i < 3; ++i) inj[i] = seq[i].cast<int>();
         if (inj[0] < 0 || inj[1] < 0 || inj[1] >= 4 || inj[2] < 0 ||
-            inj[2] >= cusweep::kPipes)
+            inj[2] >= n_pipes)
             throw std::invalid_argument(
                 "inject: block >= 0, wave in 0..3, pipe in 0.." +
-                std::to_string(cusweep::kPipes - 1));
+                std::to_string(n_pipes - 1));
     }
     if (reps < 0) throw std::invalid_argument("reps must be >= 0");
-    if (reps == 0) reps = kSweepDefaultReps;
+    if (reps == 0) reps = sweep_default_reps(set);
     if (reps > (1 << 16)) throw std::invalid_argument("reps must be <= 65536");
 
     HIP_CHECK(hipSetDevice(device));
@@ -523,10 +554,17 @@ py::dict cu_sweep(int device, int reps, py::object inject) {
     const int cu_count = props.multiProcessorCount;
     if (inj[0] >= cu_count)
         throw std::invalid_argument("inject: block must be below cu_count");
-    if ((size_t)cusweep::kTableBytes > props.sharedMemPerBlock)
+    const int lds_bytes = cusweepx::lds_bytes(set);
+    if ((size_t)lds_bytes > props.sharedMemPerBlock)
         throw std::runtime_error("the sweep tables do not fit this GPU's LDS");
 
-    static const std::vector<uint8_t> table = cusweep::build_table();
+    // built on a set's first use (under the GIL)
+    static std::vector<uint8_t> tables[cusweepx::kSets];
+    if (tables[set].empty()) tables[set] = cusweepx::build_table(set);
+    const std::vector<uint8_t> &table = tables[set];
+    auto kernel = set == cusweepx::kBase ? cu_sweep_kernel<cusweepx::kBase>
+                  : set == cusweepx::kMx ? cu_sweep_kernel<cusweepx::kMx>
+                                         : cu_sweep_kernel<cusweepx::kWide>;
     DeviceBuffer<uint4> d_table(table.size() / sizeof(uint4));
     HIP_CHECK(hipMemcpy(d_table.get(), table.data(), table.size(),
                         hipMemcpyHostToDevice));
@@ -551,9 +589,9 @@ py::dict cu_sweep(int device, int reps, py::object inject) {
         ++launches;
         HIP_CHECK(hipMemset(d_rec.get(), 0, n_rec * sizeof(SweepRecord)));
         HIP_CHECK(hipEventRecord(ev.start));
-        hipLaunchKernelGGL(cu_sweep_kernel, dim3(cu_count), dim3(256),
-                           cusweep::kTableBytes, 0, d_table.get(), d_rec.get(),
-                           reps, inj[0], inj[1], inj[2]);
+        hipLaunchKernelGGL(kernel, dim3(cu_count), dim3(256), lds_bytes, 0,
+                           d_table.get(), d_rec.get(), reps, inj[0], inj[1],
+                           inj[2]);
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipEventRecord(ev.stop));
         HIP_CHECK(hipEventSynchronize(ev.stop));
@@ -593,9 +631,9 @@ py::dict cu_sweep(int device, int reps, py::object inject) {
         b["sh"] = kv.first.sh;
         b["cu"] = kv.first.cu;
         b["simd"] = kv.first.simd;
-        b["pipes"] = sweep_pipe_names(kv.second.pipes);
+        b["pipes"] = sweep_pipe_names(set, kv.second.pipes);
         b["bad_lanes"] = kv.second.lanes;
-        b["first"] = sweep_first_failure(kv.second.first);
+        b["first"] = sweep_first_failure(set, kv.second.first);
         bad_list.append(b);
     }
     for (const auto &kv : simds_of_cu)
@@ -620,7 +658,8 @@ py::dict cu_sweep(int device, int reps, py::object inject) {
     out["launches"] = launches;
     out["reps"] = reps;  // of the last launch
     out["waves_checked"] = (uint64_t)n_rec * launches;
-    out["pipes"] = sweep_pipe_names((1u << cusweep::kPipes) - 1);
+    out["pipe_set"] = pipe_set;
+    out["pipes"] = sweep_pipe_names(set, (1u << n_pipes) - 1);
     out["bad"] = bad_list;
     out["uncovered"] = uncovered;
     out["records"] = records;
@@ -629,8 +668,71 @@ py::dict cu_sweep(int device, int reps, py::object inject) {
     return out;
 }
 
+// The tables of an extra set (mx or wide) for the tests: per test the
+// packed fragments, for mx the 64 scale words of each side and the op_sel
+// pair, and the expected result register bits; `table` is the whole blob
+// and `offset` each test's place in it (the pad a lane's 32-byte operand
+// load reads past an fp4 / fp6 fragment is what follows there).
+py::dict cu_sweep_reference_ext(int set) {
+    py::list pipes;
+    for (int p = 0; p < cusweepx::n_pipes(set); ++p) {
+        const cusweepx::PipeDesc &d = cusweepx::desc(set, p);
+        const int regs = cusweepx::ext_regs(set, p);
+        py::list tests;
+        for (int t = 0; t < cusweepx::kTests; ++t) {
+            const cusweepx::TestVector v = cusweepx::make_test(set, p, t);
+            py::list expected_bits;  // [64 lanes][regs]
+            for (int l = 0; l < cusweepx::kLanes; ++l) {
+                py::list bits;
+                for (int r = 0; r < regs; ++r)
+                    bits.append(v.expected[(size_t)l * regs + r]);
+                expected_bits.append(bits);
+            }
+            py::dict test;
+            test["a_frag"] = py::bytes((const char *)v.a_frag.data(), v.a_frag.size());
+            test["b_frag"] = py::bytes((const char *)v.b_frag.data(), v.b_frag.size());
+            if (cusweepx::scaled(set)) {
+                test["scale_a"] = v.scale_a;
+                test["scale_b"] = v.scale_b;
+                test["sel"] = py::make_tuple(cusweepx::sel_a(t), cusweepx::sel_b(t));
+            }
+            test["expected_bits"] = expected_bits;
+            test["offset"] = cusweepx::test_offset(set, p, t);
+            test["abs_sum_max"] = v.abs_sum_max;
+            test["unit_shift"] = v.unit_shift;
+            tests.append(test);
+        }
+        py::dict pipe;
+        pipe["name"] = d.name;
+        pipe["M"] = d.M;
+        pipe["N"] = d.N;
+        pipe["K"] = d.K;
+        pipe["regs"] = regs;
+        pipe["result"] = d.result == cusweepx::RF32   ? "f32"
+                         : d.result == cusweepx::RI32 ? "i32" : "f64";
+        pipe["a_format"] = cusweepx::kFmt[d.a].name;
+        pipe["b_format"] = cusweepx::kFmt[d.b].name;
+        pipe["frag_bytes_a"] = cusweepx::ext_frag_bytes(set, p, 0);
+        pipe["frag_bytes_b"] = cusweepx::ext_frag_bytes(set, p, 1);
+        pipe["tests"] = tests;
+        pipes.append(pipe);
+    }
+    const std::vector<uint8_t> table = cusweepx::build_table(set);
+    py::dict out;
+    out["pipe_set"] = cusweepx::kSetName[set];
+    out["pipes"] = pipes;
+    out["tests_per_pipe"] = cusweepx::kTests;
+    out["table_bytes"] = cusweepx::table_bytes(set);
+    out["lds_bytes"] = cusweepx::lds_bytes(set);
+    out["table"] = py::bytes((const char *)table.data(), table.size());
+    out["default_reps"] = sweep_default_reps(set);
+    return out;
+}
+
 // The sweep's tables for the tests: no HIP call, works without a GPU.
-py::dict cu_sweep_reference() {
+py::dict cu_sweep_reference(const std::string &pipe_set) {
+    const int set = sweep_set_of(pipe_set);
+    if (set != cusweepx::kBase) return cu_sweep_reference_ext(set);
     auto matrix = [](const std::vector<int> &m, int rows, int cols) {
         py::list out;
         for (int i = 0; i < rows; ++i) {
@@ -688,6 +790,98 @@ py::dict cu_sweep_reference() {
     out["table_bytes"] = cusweep::kTableBytes;
     out["default_reps"] = kSweepDefaultReps;
     return out;
+}
+
+// ---- mfma_raw: one wave, one product, caller-supplied fragments ----
+
+using RawKernel = void (*)(const unsigned char *, const unsigned char *,
+                           const uint32_t *, const uint32_t *, uint32_t *);
+
+template <int SET, int P, int... I>
+RawKernel raw_kernel_of_sel(int sel, std::integer_sequence<int, I...>) {
+    static const RawKernel kernels[] = {mfma_raw_kernel<SET, P, I / 4, I % 4>...};
+    return kernels[sel];
+}
+
+template <int SET, int... P>
+RawKernel raw_kernel_of(int p, int sel, std::integer_sequence<int, P...>) {
+    RawKernel out = nullptr;
+    auto take = [&](auto pipe) {
+        constexpr int Q = decltype(pipe)::value;
+        if (p != Q) return;
+        if constexpr (SET == cusweepx::kMx)
+            out = raw_kernel_of_sel<SET, Q>(sel, std::make_integer_sequence<int, 16>{});
+        else
+            out = mfma_raw_kernel<SET, Q, 0, 0>;
+    };
+    (take(std::integral_constant<int, P>{}), ...);
+    return out;
+}
+
+// One product of one pipe of any set on one wave, from packed per-lane
+// fragments (and, for an mx pipe, the 64 scale words of each side and the
+// byte selects) laid out as in the tables: the raw result registers,
+// [64 lanes][regs] uint32.  For the tests and for establishing operand maps
+// with one-hot data.  Names and lengths are checked before any HIP call.
+py::bytes mfma_raw(int device, const std::string &pipe, py::bytes a_frag,
+                   py::bytes b_frag, py::object scale_a, py::object scale_b,
+                   std::pair<int, int> sel) {
+    int set = -1, p = -1;
+    for (int s = 0; s < cusweepx::kSets; ++s)
+        for (int q = 0; q < cusweepx::n_pipes(s); ++q)
+            if (pipe == cusweepx::pipe_name(s, q)) {
+                set = s;
+                p = q;
+            }
+    if (set < 0) throw std::invalid_argument("mfma_raw: unknown pipe " + pipe);
+    const std::string a = a_frag, b = b_frag;
+    const size_t fa = (size_t)cusweepx::kLanes * cusweepx::frag_bytes(set, p, 0);
+    const size_t fb = (size_t)cusweepx::kLanes * cusweepx::frag_bytes(set, p, 1);
+    if (a.size() != fa || b.size() != fb)
+        throw std::invalid_argument(
+            "mfma_raw: " + pipe + " takes " + std::to_string(fa) + " bytes of A and " +
+            std::to_string(fb) + " of B");
+    if (sel.first < 0 || sel.first > 3 || sel.second < 0 || sel.second > 3)
+        throw std::invalid_argument("mfma_raw: sel is a pair of byte selects 0..3");
+    std::vector<uint32_t> scales(2 * cusweepx::kLanes, 0x7F7F7F7Fu);
+    const bool mx = cusweepx::scaled(set);
+    if (!mx && (!scale_a.is_none() || !scale_b.is_none() || sel.first || sel.second))
+        throw std::invalid_argument("mfma_raw: " + pipe + " takes no scales");
+    for (int side = 0; side < 2; ++side) {
+        const py::object &given = side ? scale_b : scale_a;
+        if (given.is_none()) continue;
+        const std::string raw = given.cast<py::bytes>();
+        if (raw.size() != 4 * (size_t)cusweepx::kLanes)
+            throw std::invalid_argument("mfma_raw: a side's scales are 64 words, 256 bytes");
+        std::memcpy(&scales[(size_t)side * cusweepx::kLanes], raw.data(), raw.size());
+    }
+    const int code = sel.first * 4 + sel.second;
+    RawKernel kernel =
+        set == cusweepx::kBase
+            ? raw_kernel_of<cusweepx::kBase>(p, code, std::make_integer_sequence<int, cusweep::kPipes>{})
+        : mx ? raw_kernel_of<cusweepx::kMx>(p, code, std::make_integer_sequence<int, cusweepx::kMxPipes>{})
+             : raw_kernel_of<cusweepx::kWide>(p, code, std::make_integer_sequence<int, cusweepx::kWidePipes>{});
+
+    HIP_CHECK(hipSetDevice(device));
+    // every lane's operand load may read 32 bytes from its fragment's start
+    constexpr size_t kPad = 32;
+    DeviceBuffer<unsigned char> d_a(fa + kPad), d_b(fb + kPad);
+    HIP_CHECK(hipMemset(d_a.get(), 0xA5, fa + kPad));
+    HIP_CHECK(hipMemset(d_b.get(), 0xA5, fb + kPad));
+    HIP_CHECK(hipMemcpy(d_a.get(), a.data(), fa, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(d_b.get(), b.data(), fb, hipMemcpyHostToDevice));
+    DeviceBuffer<uint32_t> d_s(scales.size());
+    HIP_CHECK(hipMemcpy(d_s.get(), scales.data(), scales.size() * 4,
+                        hipMemcpyHostToDevice));
+    const size_t n_out = (size_t)cusweepx::kLanes * cusweepx::regs(set, p);
+    DeviceBuffer<uint32_t> d_out(n_out);
+    HIP_CHECK(hipMemset(d_out.get(), 0xFF, n_out * 4));
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(64), 0, 0, d_a.get(), d_b.get(),
+                       d_s.get(), d_s.get() + cusweepx::kLanes, d_out.get());
+    HIP_CHECK(hipGetLastError());
+    std::vector<uint32_t> h(n_out);
+    HIP_CHECK(hipMemcpy(h.data(), d_out.get(), n_out * 4, hipMemcpyDeviceToHost));
+    return py::bytes((const char *)h.data(), n_out * 4);
 }
 
 // ---------------- HBM scrub ----------------
@@ -1568,8 +1762,13 @@ PYBIND11_MODULE(_healthprobe, m) {
     m.def("mfma_peak_check", &mfma_peak_check, py::arg("device") = 0,
           py::arg("iters") = 8192, py::arg("blocks") = 2);
     m.def("cu_sweep", &cu_sweep, py::arg("device") = 0, py::arg("reps") = 0,
-          py::arg("inject") = py::none());
-    m.def("cu_sweep_reference", &cu_sweep_reference);
+          py::arg("inject") = py::none(), py::arg("pipe_set") = "base");
+    m.def("cu_sweep_reference", &cu_sweep_reference,
+          py::arg("pipe_set") = "base");
+    m.def("mfma_raw", &mfma_raw, py::arg("device"), py::arg("pipe"),
+          py::arg("a_frag"), py::arg("b_frag"), py::arg("scale_a") = py::none(),
+          py::arg("scale_b") = py::none(),
+          py::arg("sel") = std::pair<int, int>(0, 0));
     m.def("decode_hw_id", &decode_hw_id_py, py::arg("hw_id"),
           py::arg("xcc_id"));
     m.def("hbm_scrub", &hbm_scrub, py::arg("device") = 0,

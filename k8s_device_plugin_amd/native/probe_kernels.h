@@ -6,11 +6,13 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <utility>
 
 #include "hbm_march.h"
 #include "hbm_pattern.h"
 #include "lds_march.h"
 #include "sweep_table.h"
+#include "sweep_table_ext.h"
 
 namespace {  // one translation unit per binary; keep the kernels internal
 
@@ -445,6 +447,128 @@ __device__ inline void sweep_mfma(const unsigned char *a, const unsigned char *b
 #endif
 }
 
+using f64x4 = __attribute__((ext_vector_type(4))) double;
+using i32x16 = __attribute__((ext_vector_type(16))) int;
+
+// The 8 operand registers of an f8f6f4 fragment.  The tables pack a lane's
+// fp4 / fp6 fragment into 16 / 24 bytes, so the address is only 4-byte
+// aligned and the words past the fragment are the next lane's (a pad that
+// the instruction does not read for these formats).
+__device__ inline i32x8 load_frag8(const unsigned char *p) {
+    const uint32_t *w = reinterpret_cast<const uint32_t *>(p);
+    i32x8 v;
+    for (int i = 0; i < 8; ++i) v[i] = (int)w[i];
+    return v;
+}
+
+// Set mx (cusweepx::kMxDesc): block-scaled v_mfma_scale_f32_*_f8f6f4 with
+// the lane's scale words sa / sb and the byte selects SA / SB, which the
+// instruction takes as immediates (op_sel, op_sel_hi).
+template <int P, int SA, int SB>
+__device__ inline void mx_mfma(const unsigned char *a, const unsigned char *b,
+                               uint32_t sa, uint32_t sb, uint32_t zero,
+                               uint32_t *d) {
+#if defined(__gfx950__)
+    constexpr int CA = cusweepx::kFmt[cusweepx::kMxDesc[P].a].code;
+    constexpr int CB = cusweepx::kFmt[cusweepx::kMxDesc[P].b].code;
+    const float fz = __uint_as_float(zero);
+    const i32x8 va = load_frag8(a), vb = load_frag8(b);
+    if constexpr (cusweepx::kMxDesc[P].M == 16) {
+        f32x4 c = {fz, fz, fz, fz};
+        f32x4 o = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
+            va, vb, c, CA, CB, SA, (int)sa, SB, (int)sb);
+        for (int r = 0; r < 4; ++r) d[r] = __float_as_uint(o[r]);
+    } else {
+        f32x16 c;
+        for (int r = 0; r < 16; ++r) c[r] = fz;
+        f32x16 o = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(
+            va, vb, c, CA, CB, SA, (int)sa, SB, (int)sb);
+        for (int r = 0; r < 16; ++r) d[r] = __float_as_uint(o[r]);
+    }
+#else
+    (void)a;
+    (void)b;
+    (void)sa;
+    (void)sb;
+    for (int r = 0; r < cusweepx::regs(cusweepx::kMx, P); ++r) d[r] = zero;
+#endif
+}
+
+// Set wide (cusweepx::kWideDesc): bf8, the 32x32 shapes of f16 / fp8 / i8,
+// f64 and f32-input.  An f64 result is two result registers, low word first.
+template <int P>
+__device__ inline void wide_mfma(const unsigned char *a, const unsigned char *b,
+                                 uint32_t zero, uint32_t *d) {
+#if defined(__gfx950__)
+    const float fz = __uint_as_float(zero);
+    if constexpr (P == 0) {
+        f32x4 c = {fz, fz, fz, fz};
+        f32x4 o = __builtin_amdgcn_mfma_f32_16x16x32_bf8_bf8(
+            *reinterpret_cast<const long *>(a),
+            *reinterpret_cast<const long *>(b), c, 0, 0, 0);
+        for (int r = 0; r < 4; ++r) d[r] = __float_as_uint(o[r]);
+    } else if constexpr (P == 1 || P == 2) {
+        f32x16 c;
+        for (int r = 0; r < 16; ++r) c[r] = fz;
+        f32x16 o;
+        if constexpr (P == 1)
+            o = __builtin_amdgcn_mfma_f32_32x32x16_f16(
+                *reinterpret_cast<const f16x8 *>(a),
+                *reinterpret_cast<const f16x8 *>(b), c, 0, 0, 0);
+        else
+            o = __builtin_amdgcn_mfma_f32_32x32x16_fp8_fp8(
+                *reinterpret_cast<const long *>(a),
+                *reinterpret_cast<const long *>(b), c, 0, 0, 0);
+        for (int r = 0; r < 16; ++r) d[r] = __float_as_uint(o[r]);
+    } else if constexpr (P == 3) {
+        const int iz = (int)zero;
+        i32x16 c;
+        for (int r = 0; r < 16; ++r) c[r] = iz;
+        i32x16 o = __builtin_amdgcn_mfma_i32_32x32x32_i8(
+            *reinterpret_cast<const i32x4 *>(a),
+            *reinterpret_cast<const i32x4 *>(b), c, 0, 0, 0);
+        for (int r = 0; r < 16; ++r) d[r] = (uint32_t)o[r];
+    } else if constexpr (P == 4) {
+        const double dz = __longlong_as_double((long long)zero);
+        f64x4 c = {dz, dz, dz, dz};
+        f64x4 o = __builtin_amdgcn_mfma_f64_16x16x4f64(
+            *reinterpret_cast<const double *>(a),
+            *reinterpret_cast<const double *>(b), c, 0, 0, 0);
+        for (int r = 0; r < 4; ++r) {
+            const unsigned long long bits =
+                (unsigned long long)__double_as_longlong(o[r]);
+            d[2 * r] = (uint32_t)bits;
+            d[2 * r + 1] = (uint32_t)(bits >> 32);
+        }
+    } else {
+        static_assert(P == 5, "six pipes");
+        f32x4 c = {fz, fz, fz, fz};
+        f32x4 o = __builtin_amdgcn_mfma_f32_16x16x4f32(
+            *reinterpret_cast<const float *>(a),
+            *reinterpret_cast<const float *>(b), c, 0, 0, 0);
+        for (int r = 0; r < 4; ++r) d[r] = __float_as_uint(o[r]);
+    }
+#else
+    (void)a;
+    (void)b;
+    for (int r = 0; r < cusweepx::regs(cusweepx::kWide, P); ++r) d[r] = zero;
+#endif
+}
+
+// pipe P of set SET (cusweepx::Set): the base set's sweep_mfma or one of the
+// two above
+template <int SET, int P, int SA, int SB>
+__device__ inline void set_mfma(const unsigned char *a, const unsigned char *b,
+                                uint32_t sa, uint32_t sb, uint32_t zero,
+                                uint32_t *d) {
+    if constexpr (SET == cusweepx::kBase)
+        sweep_mfma<P>(a, b, zero, d);
+    else if constexpr (SET == cusweepx::kMx)
+        mx_mfma<P, SA, SB>(a, b, sa, sb, zero, d);
+    else
+        wide_mfma<P>(a, b, zero, d);
+}
+
 // wave-uniform running state of one wave's sweep
 struct SweepWaveState {
     uint32_t fail_pipes = 0;
@@ -452,64 +576,105 @@ struct SweepWaveState {
     bool have_first = false;
 };
 
-template <int P>
-__device__ inline void sweep_pipe(const unsigned char *table, int lane,
+// test t of pipe P of set SET; SA / SB are that test's byte selects (mx)
+template <int SET, int P, int SA, int SB>
+__device__ inline void sweep_test(const unsigned char *table, int t, int lane,
                                   uint32_t zero, bool inject,
                                   SweepWaveState &st, SweepRecord *rec) {
-    constexpr int FB = cusweep::frag_bytes(P), R = cusweep::kPipeDesc[P].regs;
-    for (int t = 0; t < cusweep::kTests; ++t) {
-        const unsigned char *a = table + cusweep::test_offset(P, t);
-        const unsigned char *b = a + cusweep::kLanes * FB;
-        const uint32_t *want =
-            reinterpret_cast<const uint32_t *>(b + cusweep::kLanes * FB) + lane * R;
-        uint32_t d[R];
-        sweep_mfma<P>(a + lane * FB, b + lane * FB, zero, d);
-        if (inject && lane == kSweepInjectLane) d[kSweepInjectReg] ^= kSweepInjectBit;
-        int bad_reg = -1;  // the lowest mismatching register of this lane
-        uint32_t got = 0, expected = 0;
+    constexpr int FA = cusweepx::frag_bytes(SET, P, 0),
+                  FB = cusweepx::frag_bytes(SET, P, 1),
+                  R = cusweepx::regs(SET, P);
+    const unsigned char *a = table + cusweepx::test_offset(SET, P, t);
+    const unsigned char *b = a + cusweep::kLanes * FA;
+    const uint32_t *want = reinterpret_cast<const uint32_t *>(b + cusweep::kLanes * FB);
+    uint32_t sa = 0, sb = 0;
+    if constexpr (cusweepx::scaled(SET)) {
+        sa = want[lane];
+        sb = want[cusweep::kLanes + lane];
+        want += 2 * cusweep::kLanes;
+    }
+    want += lane * R;
+    uint32_t d[R];
+    set_mfma<SET, P, SA, SB>(a + lane * FA, b + lane * FB, sa, sb, zero, d);
+    if (inject && lane == kSweepInjectLane) d[kSweepInjectReg] ^= kSweepInjectBit;
+    int bad_reg = -1;  // the lowest mismatching register of this lane
+    uint32_t got = 0, expected = 0;
 #pragma unroll
-        for (int r = R - 1; r >= 0; --r)
-            if (d[r] != want[r]) {
-                bad_reg = r;
-                got = d[r];
-                expected = want[r];
-            }
-        unsigned long long ballot = __ballot(bad_reg >= 0);
-        if (ballot) {
-            st.fail_pipes |= 1u << P;
-            st.bad_lanes |= ballot;
-            if (!st.have_first) {
-                st.have_first = true;
-                // the lowest bad lane reports its own registers
-                if (lane == __ffsll((long long)ballot) - 1) {
-                    rec->first_pipe = P;
-                    rec->first_t = t;
-                    rec->first_lane = lane;
-                    rec->first_reg = bad_reg;
-                    rec->first_got = got;
-                    rec->first_expected = expected;
-                }
+    for (int r = R - 1; r >= 0; --r)
+        if (d[r] != want[r]) {
+            bad_reg = r;
+            got = d[r];
+            expected = want[r];
+        }
+    unsigned long long ballot = __ballot(bad_reg >= 0);
+    if (ballot) {
+        st.fail_pipes |= 1u << P;
+        st.bad_lanes |= ballot;
+        if (!st.have_first) {
+            st.have_first = true;
+            // the lowest bad lane reports its own registers
+            if (lane == __ffsll((long long)ballot) - 1) {
+                rec->first_pipe = P;
+                rec->first_t = t;
+                rec->first_lane = lane;
+                rec->first_reg = bad_reg;
+                rec->first_got = got;
+                rec->first_expected = expected;
             }
         }
     }
 }
 
-// One 4-wave block per CU.  The block copies the packed operand and
-// expected-result tables (sweep_table.h) into LDS, cusweep::kTableBytes of
-// dynamic LDS: more than half of the CU's 160 KiB, so no two sweep blocks
-// share a CU.  Each wave then reads where it runs from the hardware id
-// registers, runs reps rounds of every pipe's known-answer products on its
-// SIMD and compares every result register bit for bit.  Nothing here
-// depends on where a block lands and no block waits for another; the host
-// works out the coverage from the records.
+// the tests of an mx pipe, unrolled: each has its own byte selects
+template <int P, int... T>
+__device__ inline void sweep_mx_tests(std::integer_sequence<int, T...>,
+                                      const unsigned char *table, int lane,
+                                      uint32_t zero, bool inject,
+                                      SweepWaveState &st, SweepRecord *rec) {
+    (sweep_test<cusweepx::kMx, P, cusweepx::sel_a(T), cusweepx::sel_b(T)>(
+         table, T, lane, zero, inject, st, rec),
+     ...);
+}
+
+template <int SET, int P>
+__device__ inline void sweep_pipe(const unsigned char *table, int lane,
+                                  uint32_t zero, bool inject,
+                                  SweepWaveState &st, SweepRecord *rec) {
+    if constexpr (SET == cusweepx::kMx) {
+        sweep_mx_tests<P>(std::make_integer_sequence<int, cusweepx::kTests>{},
+                          table, lane, zero, inject, st, rec);
+    } else {
+        for (int t = 0; t < cusweepx::n_tests(SET); ++t)
+            sweep_test<SET, P, 0, 0>(table, t, lane, zero, inject, st, rec);
+    }
+}
+
+template <int SET, int... P>
+__device__ inline void sweep_pipes(std::integer_sequence<int, P...>,
+                                   const unsigned char *table, int lane,
+                                   uint32_t zero, bool mine, int inject_pipe,
+                                   SweepWaveState &st, SweepRecord *rec) {
+    (sweep_pipe<SET, P>(table, lane, zero, mine && inject_pipe == P, st, rec), ...);
+}
+
+// One 4-wave block per CU, for pipe set SET (cusweepx::Set: the base set of
+// sweep_table.h, or mx / wide of sweep_table_ext.h).  The block copies the
+// set's packed operand and expected-result table into LDS; the launch asks
+// for cusweepx::lds_bytes(SET) of dynamic LDS, more than half of the CU's
+// 160 KiB, so no two sweep blocks share a CU.  Each wave then reads where it
+// runs from the hardware id registers, runs reps rounds of every pipe's
+// known-answer products on its SIMD and compares every result register bit
+// for bit.  Nothing here depends on where a block lands and no block waits
+// for another; the host works out the coverage from the records.
 // inject_block / inject_wave / inject_pipe (-1 = off) make that one wave
 // flip one bit of one result register of that pipe before comparing: a bad
 // pipe simulated on healthy hardware.
+template <int SET>
 __global__ void __launch_bounds__(256)
 cu_sweep_kernel(const uint4 *__restrict__ table, SweepRecord *records, int reps,
                 int inject_block, int inject_wave, int inject_pipe) {
     extern __shared__ uint4 sweep_lds[];
-    for (int i = threadIdx.x; i < cusweep::kTableBytes / 16; i += blockDim.x)
+    for (int i = threadIdx.x; i < cusweepx::table_bytes(SET) / 16; i += blockDim.x)
         sweep_lds[i] = table[i];
     __syncthreads();
 
@@ -524,12 +689,8 @@ cu_sweep_kernel(const uint4 *__restrict__ table, SweepRecord *records, int reps,
     for (int rep = 0; rep < reps; ++rep) {
         uint32_t zero = 0;
         asm volatile("" : "+v"(zero));
-        sweep_pipe<0>(tbl, lane, zero, mine && inject_pipe == 0, st, rec);
-        sweep_pipe<1>(tbl, lane, zero, mine && inject_pipe == 1, st, rec);
-        sweep_pipe<2>(tbl, lane, zero, mine && inject_pipe == 2, st, rec);
-        sweep_pipe<3>(tbl, lane, zero, mine && inject_pipe == 3, st, rec);
-        sweep_pipe<4>(tbl, lane, zero, mine && inject_pipe == 4, st, rec);
-        sweep_pipe<5>(tbl, lane, zero, mine && inject_pipe == 5, st, rec);
+        sweep_pipes<SET>(std::make_integer_sequence<int, cusweepx::n_pipes(SET)>{},
+                         tbl, lane, zero, mine, inject_pipe, st, rec);
     }
     if (lane == 0) {
         rec->hw_id = hw_id;
@@ -538,6 +699,26 @@ cu_sweep_kernel(const uint4 *__restrict__ table, SweepRecord *records, int reps,
         rec->bad_lanes_lo = (uint32_t)st.bad_lanes;
         rec->bad_lanes_hi = (uint32_t)(st.bad_lanes >> 32);
     }
+}
+
+// One wave, one product of pipe P of set SET from caller-supplied packed
+// fragments and scale words (mfma_raw): out[lane * regs + r].  a and b are
+// readable for 32 bytes from every lane's fragment.
+template <int SET, int P, int SA, int SB>
+__global__ void __launch_bounds__(64)
+mfma_raw_kernel(const unsigned char *__restrict__ a,
+                const unsigned char *__restrict__ b,
+                const uint32_t *__restrict__ scale_a,
+                const uint32_t *__restrict__ scale_b, uint32_t *out) {
+    constexpr int R = cusweepx::regs(SET, P);
+    const int lane = threadIdx.x;
+    uint32_t zero = 0;
+    asm volatile("" : "+v"(zero));
+    uint32_t d[R];
+    set_mfma<SET, P, SA, SB>(a + lane * cusweepx::frag_bytes(SET, P, 0),
+                             b + lane * cusweepx::frag_bytes(SET, P, 1),
+                             scale_a[lane], scale_b[lane], zero, d);
+    for (int r = 0; r < R; ++r) out[lane * R + r] = d[r];
 }
 
 // ---------------- LDS sweep: march over one CU's whole LDS ----------------

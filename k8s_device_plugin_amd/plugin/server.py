@@ -61,6 +61,7 @@ class AMDGPUPlugin:
         dev_root: str = "/dev",
         deep_cu_sweep: bool = False,
         deep_lds_sweep: bool = False,
+        deep_cu_sweep_extra=(),
     ):
         self.resource = resource
         self.cdi_enabled = cdi_enabled
@@ -85,6 +86,9 @@ class AMDGPUPlugin:
         # of the physical GPU (in CPX mode each partition is an ordinal of
         # its own, so all XCDs are covered)
         self.deep_cu_sweep = deep_cu_sweep
+        # the extra pipe sets ("mx", "wide") swept wherever the base sweep
+        # runs; _sweep_bad_simds counts distinct SIMDs over all sets
+        self.deep_cu_sweep_extra = tuple(deep_cu_sweep_extra)
         self._sweep_bad_simds: Dict[str, int] = {}  # dev_id -> last count
         # likewise the march test of every CU's whole LDS (LDS sweep), on
         # every ordinal; independent of the CU sweep
@@ -235,22 +239,32 @@ class AMDGPUPlugin:
         res = deep_health_probe(device=ordinals[0], hbm_scrub_bytes=0, **sweeps)
         if self.deep_cu_sweep:
             res["cu_sweep"] = {}
-            bad_simds = 0
+            if self.deep_cu_sweep_extra:
+                res["cu_sweep_extra"] = {s: {} for s in self.deep_cu_sweep_extra}
+            bad_simds = set()  # a SIMD that fails in two sets counts once
             for ordinal in ordinals:
-                sweep = run_cu_sweep(ordinal)
-                res["cu_sweep"][ordinal] = sweep
-                bad_simds += len(sweep.get("bad", []))
-                for line in cu_sweep_violations(sweep):
-                    line = f"{line} (hip device {ordinal})"
-                    log.error("deep probe on %s: %s", dev.dev_id, line)
-                    res["floor_violations"].append(line)
-                if sweep.get("ok") and not sweep.get("coverage_complete"):
-                    log.warning(
-                        "deep probe on %s: cu_sweep reached %s of %s CUs on "
-                        "hip device %d", dev.dev_id, sweep.get("cus_covered"),
-                        sweep.get("cu_count"), ordinal,
-                    )
-            self._sweep_bad_simds[dev.dev_id] = bad_simds
+                for pipe_set in ("base",) + self.deep_cu_sweep_extra:
+                    if pipe_set == "base":
+                        sweep = run_cu_sweep(ordinal)
+                        res["cu_sweep"][ordinal] = sweep
+                    else:
+                        sweep = run_cu_sweep(ordinal, pipe_set=pipe_set)
+                        res["cu_sweep_extra"][pipe_set][ordinal] = sweep
+                    for b in sweep.get("bad", []):
+                        bad_simds.add((ordinal, b["xcc"], b["se"], b["sh"],
+                                       b["cu"], b["simd"]))
+                    for line in cu_sweep_violations(sweep):
+                        line = f"{line} (hip device {ordinal})"
+                        log.error("deep probe on %s: %s", dev.dev_id, line)
+                        res["floor_violations"].append(line)
+                    if sweep.get("ok") and not sweep.get("coverage_complete"):
+                        log.warning(
+                            "deep probe on %s: cu_sweep (%s pipes) reached %s "
+                            "of %s CUs on hip device %d", dev.dev_id, pipe_set,
+                            sweep.get("cus_covered"), sweep.get("cu_count"),
+                            ordinal,
+                        )
+            self._sweep_bad_simds[dev.dev_id] = len(bad_simds)
             if bad_simds:
                 res["healthy"] = False
         if self.deep_lds_sweep:
