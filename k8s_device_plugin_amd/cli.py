@@ -80,6 +80,14 @@ def device_plugin_main(argv=None) -> int:
                          "march-test the whole LDS of every CU through every "
                          "route into it, on every HIP device of the GPU, and "
                          "pin a GPU with a bad CU Unhealthy")
+    ap.add_argument("--deep-probe-valu-sweep", nargs="?", const="all", default="",
+                    metavar="fma,int,cvt,xlane,salu,trans|all",
+                    help="with --deep-probe-every / --prestart-deep: also "
+                         "run known-answer vector, conversion, cross-lane, "
+                         "scalar and transcendental ops on every SIMD of "
+                         "every CU, on every HIP device of the GPU, and pin "
+                         "a GPU with a bad SIMD Unhealthy; the bare flag "
+                         "means all sets")
     ap.add_argument("--dump", action="store_true",
                     help="print discovered devices + allocator state as "
                          "JSON and exit (debugging)")
@@ -96,7 +104,7 @@ def device_plugin_main(argv=None) -> int:
                          "behavior); default is in-process re-registration")
     ap.add_argument("-v", "--verbose", action="count", default=0)
     args = ap.parse_args(argv)
-    from .native import cu_sweep_extra_sets
+    from .native import cu_sweep_extra_sets, valu_sweep_sets
 
     try:
         sweep_extra = cu_sweep_extra_sets(args.deep_probe_cu_sweep_extra)
@@ -104,6 +112,10 @@ def device_plugin_main(argv=None) -> int:
         ap.error(f"--deep-probe-cu-sweep-extra: {e}")
     if sweep_extra and not args.deep_probe_cu_sweep:
         ap.error("--deep-probe-cu-sweep-extra requires --deep-probe-cu-sweep")
+    try:
+        valu_sets = valu_sweep_sets(args.deep_probe_valu_sweep)
+    except ValueError as e:
+        ap.error(f"--deep-probe-valu-sweep: {e}")
     _setup_logging(args.verbose)
     log = logging.getLogger("amd-device-plugin")
     # startup banner (reference: main.go:94-121 logs name+version lines)
@@ -219,6 +231,7 @@ def device_plugin_main(argv=None) -> int:
                                  deep_cu_sweep=args.deep_probe_cu_sweep,
                                  deep_cu_sweep_extra=sweep_extra,
                                  deep_lds_sweep=args.deep_probe_lds_sweep,
+                                 deep_valu_sweep=valu_sets,
                                  exit_on_stream_loss=args.exit_on_stream_loss),
         device_plugin_path=args.kubelet_dir or dp.DEVICE_PLUGIN_PATH,
         server_impl=args.server,

@@ -200,6 +200,106 @@ def cu_sweep_incomplete_warning(sweep: dict, pipe_set: str = "base"):
         sweep.get("simds_covered"))
 
 
+VALU_SWEEP_ENV = "AMDXDP_VALU_SWEEP"
+VALU_SWEEP_INJECT_ENV = "AMDXDP_VALU_SWEEP_INJECT"
+# the op sets of native/valu_table.h, in its order
+VALU_SWEEP_SETS = ("fma", "int", "cvt", "xlane", "salu", "trans")
+
+
+def valu_sweep_sets(valu_sweep=None) -> tuple:
+    """The VALU op sets to sweep, in the order of VALU_SWEEP_SETS.  An
+    explicit argument wins: False or True (none, all), "all", a comma list or
+    an iterable of set names; None reads AMDXDP_VALU_SWEEP (unset, empty or
+    0 = none, 1 or all = every set, otherwise a comma list)."""
+    spec = valu_sweep
+    if spec is None:
+        spec = os.environ.get(VALU_SWEEP_ENV, "")
+    if spec is False:
+        return ()
+    if spec is True:
+        return VALU_SWEEP_SETS
+    if isinstance(spec, str):
+        spec = [s.strip() for s in spec.split(",") if s.strip()]
+    names = [str(s).strip().lower() for s in spec]
+    if names in (["0"], []):
+        return ()
+    if "all" in names or "1" in names:
+        if len(names) != 1:
+            raise ValueError("valu_sweep: all stands alone")
+        return VALU_SWEEP_SETS
+    for name in names:
+        if name not in VALU_SWEEP_SETS:
+            raise ValueError(
+                f"valu_sweep: unknown op set {name!r}, expected all or "
+                "some of " + ", ".join(VALU_SWEEP_SETS))
+    return tuple(s for s in VALU_SWEEP_SETS if s in names)
+
+
+def _valu_op_names(mod, op_set: str) -> list:
+    return [op["name"] for op in mod.valu_sweep_reference(op_set)["ops"]]
+
+
+def _valu_inject_from_env(mod, op_set: str):
+    """AMDXDP_VALU_SWEEP_INJECT="block:wave:op" -> (block, wave, index) for
+    the set that owns the op, None for every other set: the sweep then
+    simulates one bad op on healthy hardware.  op is the op's name."""
+    spec = os.environ.get(VALU_SWEEP_INJECT_ENV, "").strip()
+    if not spec:
+        return None
+    fields = spec.split(":")
+    try:
+        if len(fields) != 3:
+            raise ValueError
+        block, wave = (int(x) for x in fields[:2])
+        name = fields[2].strip()
+        owner = next(s for s in VALU_SWEEP_SETS
+                     if name in _valu_op_names(mod, s))
+    except (ValueError, StopIteration):
+        raise ValueError(
+            f"{VALU_SWEEP_INJECT_ENV}={spec!r}: expected block:wave:op, op "
+            "the name of an op of one of the sets"
+        ) from None
+    if owner != op_set:
+        return None
+    return (block, wave, _valu_op_names(mod, owner).index(name))
+
+
+def run_valu_sweep(device: int = 0, mod=None, op_set: str = "fma") -> dict:
+    """Known-answer sweep of one VALU op set (VALU_SWEEP_SETS) over every CU
+    and SIMD of one HIP device."""
+    if mod is None:
+        mod = load_healthprobe(required=True)
+    inject = _valu_inject_from_env(mod, op_set)
+    return mod.valu_sweep(device=device, inject=inject, op_set=op_set)
+
+
+def valu_sweep_violations(sweep: dict, op_set: str = "") -> list:
+    """One line per SIMD that failed the sweep of one set.  The scalar unit
+    belongs to the CU: for set salu the SIMD is only where it was seen."""
+    lines = []
+    for b in sweep.get("bad", []):
+        ops = ", ".join(b["ops"])
+        if op_set == "salu":
+            lines.append(
+                "valu_sweep: xcc {} se {} cu {} scalar unit failed {} "
+                "(seen by simd {})".format(b["xcc"], b["se"], b["cu"], ops,
+                                           b["simd"]))
+        else:
+            lines.append("valu_sweep: xcc {} se {} cu {} simd {} failed {}".format(
+                b["xcc"], b["se"], b["cu"], b["simd"], ops))
+    return lines
+
+
+def valu_sweep_incomplete_warning(sweep: dict, op_set: str):
+    """The warning line of a set's sweep that found nothing bad but could
+    not reach every SIMD, or None."""
+    if not sweep.get("ok") or sweep.get("coverage_complete"):
+        return None
+    return "valu_sweep_incomplete[{}]: {} of {} CUs, {} SIMDs".format(
+        op_set, sweep.get("cus_covered"), sweep.get("cu_count"),
+        sweep.get("simds_covered"))
+
+
 LDS_SWEEP_ENV = "AMDXDP_LDS_SWEEP"
 LDS_SWEEP_INJECT_ENV = "AMDXDP_LDS_SWEEP_INJECT"
 
@@ -420,6 +520,7 @@ def deep_health_probe(
     lds_sweep: Optional[bool] = None,
     sysroot: str = "/",
     cu_sweep_extra=None,
+    valu_sweep=None,
 ) -> dict:
     """Run the on-GPU MFMA/LDS/HBM probe and apply performance floors.
 
@@ -449,6 +550,13 @@ def deep_health_probe(
     not own every CU's LDS only warns.  The gfx RAS counters under sysroot
     are read before and after (`ecc`, None when unreadable): corrected
     errors during the sweep warn, uncorrectable ones are a violation.
+
+    valu_sweep (None = env AMDXDP_VALU_SWEEP, default off; True, "all" or an
+    iterable of VALU_SWEEP_SETS) adds the known-answer sweep of the vector,
+    conversion, cross-lane, scalar and transcendental ops under `valu_sweep`
+    as {set: dict}: a SIMD (set salu: a CU's scalar unit) with a wrong result
+    makes the GPU unhealthy, with one violation line per SIMD and set; a
+    clean but incomplete set only warns.
     """
     if mfma_floor_tflops is None:
         mfma_floor_tflops = _floor_from_env(MFMA_FLOOR_ENV,
@@ -458,6 +566,7 @@ def deep_health_probe(
                                          DEFAULT_HBM_FLOOR_GBPS)
     if cu_sweep_extra is not None:
         cu_sweep_extra = cu_sweep_extra_sets(cu_sweep_extra)  # or ValueError
+    valu_sets = valu_sweep_sets(valu_sweep)  # or ValueError
     mod = load_healthprobe(required=True)
     res = mod.run_probe(device=device, hbm_bytes=hbm_bytes)
     violations = []
@@ -499,6 +608,13 @@ def deep_health_probe(
         violations.extend(sweep["violations"])
         if sweep["warnings"]:
             res.setdefault("warnings", []).extend(sweep["warnings"])
+    for op_set in valu_sets:
+        sweep = run_valu_sweep(device, mod, op_set)
+        res.setdefault("valu_sweep", {})[op_set] = sweep
+        violations.extend(valu_sweep_violations(sweep, op_set))
+        warning = valu_sweep_incomplete_warning(sweep, op_set)
+        if warning:
+            res.setdefault("warnings", []).append(warning)
     scrub_bytes = hbm_scrub_bytes_from_env(hbm_scrub_bytes)
     if scrub_bytes is not None:
         scrub = hbm_scrub(device, scrub_bytes, mod=mod)

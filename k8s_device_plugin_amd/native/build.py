@@ -57,7 +57,9 @@ def build_drmctl(force: bool = False) -> str:
 _HIP_HEADERS = [os.path.join(PKG_DIR, h)
                 for h in ("hip_util.h", "probe_kernels.h",
                           "sweep_table.h", "sweep_table_ext.h",
-                          "hbm_pattern.h", "hbm_march.h", "lds_march.h")]
+                          "hbm_pattern.h", "hbm_march.h", "lds_march.h",
+                          "valu_kernels.h", "valu_table.h",
+                          "valu_trans_gfx950.inc")]
 
 
 def build_healthprobe(force: bool = False) -> str:

@@ -22,7 +22,11 @@
 //   7. on request (lds_sweep), the same march over all 160 KiB of LDS of
 //      every CU, through the 128-, 64- and 32-bit loads and stores, the
 //      LDS-DMA and the transposed read (lds_march.h), with the place each
-//      block ran read from the hardware id registers.
+//      block ran read from the hardware id registers;
+//   8. on request (valu_sweep), known-answer vector, conversion, cross-lane,
+//      scalar and transcendental instructions on every SIMD of every CU, in
+//      the CU sweep's shape and with its host code (valu_kernels.h,
+//      valu_table.h).
 //
 // Used by the plugin's optional deep health check, __graft_entry__.smoke(),
 // and the gpu-marked tests.  The kernels live in probe_kernels.h (shared
@@ -46,6 +50,7 @@
 
 #include "hip_util.h"
 #include "probe_kernels.h"
+#include "valu_kernels.h"
 
 namespace py = pybind11;
 
@@ -502,17 +507,33 @@ int sweep_set_of(const std::string &name) {
     throw std::invalid_argument("pipe_set must be base, mx or wide, not " + name);
 }
 
-py::list sweep_pipe_names(int set, uint32_t mask) {
+// What one kind of sweep (CU sweep, VALU sweep) hands to the shared runner:
+// its kernel for one set, the set's table and LDS request, and how its
+// units (pipes, ops) are called.
+using SweepKernel = void (*)(const uint4 *, SweepRecord *, int, int, int, int);
+
+struct SweepSpec {
+    SweepKernel kernel;
+    const std::vector<uint8_t> *table;
+    int lds_bytes;
+    int n_units;
+    const char *(*unit_name)(int set, int unit);
+    int set;
+    const char *unit_key;   // "pipe" / "op"
+    const char *units_key;  // "pipes" / "ops"
+};
+
+py::list sweep_unit_names(const SweepSpec &spec, uint32_t mask) {
     py::list names;
-    for (int p = 0; p < cusweepx::n_pipes(set); ++p)
-        if (mask >> p & 1) names.append(cusweepx::pipe_name(set, p));
+    for (int p = 0; p < spec.n_units; ++p)
+        if (mask >> p & 1) names.append(spec.unit_name(spec.set, p));
     return names;
 }
 
-py::dict sweep_first_failure(int set, const SweepRecord &r) {
+py::dict sweep_first_failure(const SweepSpec &spec, const SweepRecord &r) {
     py::dict first;
-    first["pipe"] = r.first_pipe < (uint32_t)cusweepx::n_pipes(set)
-                        ? cusweepx::pipe_name(set, (int)r.first_pipe) : "?";
+    first[spec.unit_key] = r.first_pipe < (uint32_t)spec.n_units
+                               ? spec.unit_name(spec.set, (int)r.first_pipe) : "?";
     first["t"] = r.first_t;
     first["lane"] = r.first_lane;
     first["reg"] = r.first_reg;
@@ -521,50 +542,46 @@ py::dict sweep_first_failure(int set, const SweepRecord &r) {
     return first;
 }
 
-// Known-answer MFMA products on every SIMD of every CU (cu_sweep_kernel).
+// inject = (block, wave, unit) or None -> inj[3], -1 = off
+void parse_sweep_inject(py::object inject, int n_units, const char *unit_key,
+                        int inj[3]) {
+    inj[0] = inj[1] = inj[2] = -1;
+    if (inject.is_none()) return;
+    const std::string unit = unit_key;
+    py::sequence seq = inject.cast<py::sequence>();
+    if (py::len(seq) != 3)
+        throw std::invalid_argument("inject must be (block, wave, " + unit + ")");
+    for (int i = 0; i < 3; ++i) inj[i] = seq[i].cast<int>();
+    if (inj[0] < 0 || inj[1] < 0 || inj[1] >= 4 || inj[2] < 0 || inj[2] >= n_units)
+        throw std::invalid_argument(
+            "inject: block >= 0, wave in 0..3, " + unit + " in 0.." +
+            std::to_string(n_units - 1));
+}
+
+int checked_sweep_reps(int reps, int default_reps) {
+    if (reps < 0) throw std::invalid_argument("reps must be >= 0");
+    if (reps == 0) reps = default_reps;
+    if (reps > (1 << 16)) throw std::invalid_argument("reps must be <= 65536");
+    return reps;
+}
+
+// The host side of a known-answer sweep (cu_sweep_kernel, valu_sweep_kernel).
 // One launch of cu_count blocks; where the records show a SIMD that no wave
 // ran on, launch again with doubled reps (longer-lived blocks overlap more
 // surely), at most kSweepMaxLaunches in all, accumulating coverage and
-// failures.  inject = (block, wave, pipe) simulates one bad pipe.  pipe_set
-// chooses the pipes: "base" (sweep_table.h), "mx" or "wide"
-// (sweep_table_ext.h); pipe indices and names are the set's own.
-py::dict cu_sweep(int device, int reps, py::object inject,
-                  const std::string &pipe_set) {
-    const int set = sweep_set_of(pipe_set);
-    const int n_pipes = cusweepx::n_pipes(set);
-    int inj[3] = {-1, -1, -1};
-    if (!inject.is_none()) {
-        py::sequence seq = inject.cast<py::sequence>();
-        if (py::len(seq) != 3)
-            throw std::invalid_argument("inject must be (block, wave, pipe)");
-        for (int i = 0; i < 3; ++i) inj[i] = seq[i].cast<int>();
-        if (inj[0] < 0 || inj[1] < 0 || inj[1] >= 4 || inj[2] < 0 ||
-            inj[2] >= n_pipes)
-            throw std::invalid_argument(
-                "inject: block >= 0, wave in 0..3, pipe in 0.." +
-                std::to_string(n_pipes - 1));
-    }
-    if (reps < 0) throw std::invalid_argument("reps must be >= 0");
-    if (reps == 0) reps = sweep_default_reps(set);
-    if (reps > (1 << 16)) throw std::invalid_argument("reps must be <= 65536");
-
+// failures.  inj = (block, wave, unit) simulates one bad unit, -1 = off.
+py::dict run_sweep(int device, int reps, const int inj[3], const SweepSpec &spec) {
     HIP_CHECK(hipSetDevice(device));
     hipDeviceProp_t props;
     HIP_CHECK(hipGetDeviceProperties(&props, device));
     const int cu_count = props.multiProcessorCount;
     if (inj[0] >= cu_count)
         throw std::invalid_argument("inject: block must be below cu_count");
-    const int lds_bytes = cusweepx::lds_bytes(set);
+    const int lds_bytes = spec.lds_bytes;
     if ((size_t)lds_bytes > props.sharedMemPerBlock)
         throw std::runtime_error("the sweep tables do not fit this GPU's LDS");
 
-    // built on a set's first use (under the GIL)
-    static std::vector<uint8_t> tables[cusweepx::kSets];
-    if (tables[set].empty()) tables[set] = cusweepx::build_table(set);
-    const std::vector<uint8_t> &table = tables[set];
-    auto kernel = set == cusweepx::kBase ? cu_sweep_kernel<cusweepx::kBase>
-                  : set == cusweepx::kMx ? cu_sweep_kernel<cusweepx::kMx>
-                                         : cu_sweep_kernel<cusweepx::kWide>;
+    const std::vector<uint8_t> &table = *spec.table;
     DeviceBuffer<uint4> d_table(table.size() / sizeof(uint4));
     HIP_CHECK(hipMemcpy(d_table.get(), table.data(), table.size(),
                         hipMemcpyHostToDevice));
@@ -589,7 +606,7 @@ py::dict cu_sweep(int device, int reps, py::object inject,
         ++launches;
         HIP_CHECK(hipMemset(d_rec.get(), 0, n_rec * sizeof(SweepRecord)));
         HIP_CHECK(hipEventRecord(ev.start));
-        hipLaunchKernelGGL(kernel, dim3(cu_count), dim3(256), lds_bytes, 0,
+        hipLaunchKernelGGL(spec.kernel, dim3(cu_count), dim3(256), lds_bytes, 0,
                            d_table.get(), d_rec.get(), reps, inj[0], inj[1],
                            inj[2]);
         HIP_CHECK(hipGetLastError());
@@ -631,9 +648,9 @@ py::dict cu_sweep(int device, int reps, py::object inject,
         b["sh"] = kv.first.sh;
         b["cu"] = kv.first.cu;
         b["simd"] = kv.first.simd;
-        b["pipes"] = sweep_pipe_names(set, kv.second.pipes);
+        b[spec.units_key] = sweep_unit_names(spec, kv.second.pipes);
         b["bad_lanes"] = kv.second.lanes;
-        b["first"] = sweep_first_failure(set, kv.second.first);
+        b["first"] = sweep_first_failure(spec, kv.second.first);
         bad_list.append(b);
     }
     for (const auto &kv : simds_of_cu)
@@ -658,13 +675,37 @@ py::dict cu_sweep(int device, int reps, py::object inject,
     out["launches"] = launches;
     out["reps"] = reps;  // of the last launch
     out["waves_checked"] = (uint64_t)n_rec * launches;
-    out["pipe_set"] = pipe_set;
-    out["pipes"] = sweep_pipe_names(set, (1u << n_pipes) - 1);
+    out[spec.units_key] = sweep_unit_names(spec, ~0u);
     out["bad"] = bad_list;
     out["uncovered"] = uncovered;
     out["records"] = records;
     out["sweep_ms"] = sweep_ms;
     out["ok"] = bad.empty();
+    return out;
+}
+
+// Known-answer MFMA products on every SIMD of every CU (cu_sweep_kernel,
+// run_sweep).  inject = (block, wave, pipe) simulates one bad pipe.  pipe_set
+// chooses the pipes: "base" (sweep_table.h), "mx" or "wide"
+// (sweep_table_ext.h); pipe indices and names are the set's own.
+py::dict cu_sweep(int device, int reps, py::object inject,
+                  const std::string &pipe_set) {
+    const int set = sweep_set_of(pipe_set);
+    int inj[3];
+    parse_sweep_inject(inject, cusweepx::n_pipes(set), "pipe", inj);
+    reps = checked_sweep_reps(reps, sweep_default_reps(set));
+
+    // built on a set's first use (under the GIL)
+    static std::vector<uint8_t> tables[cusweepx::kSets];
+    if (tables[set].empty()) tables[set] = cusweepx::build_table(set);
+    const SweepSpec spec = {
+        set == cusweepx::kBase ? cu_sweep_kernel<cusweepx::kBase>
+        : set == cusweepx::kMx ? cu_sweep_kernel<cusweepx::kMx>
+                               : cu_sweep_kernel<cusweepx::kWide>,
+        &tables[set], cusweepx::lds_bytes(set), cusweepx::n_pipes(set),
+        [](int s, int p) { return cusweepx::pipe_name(s, p); }, set, "pipe", "pipes"};
+    py::dict out = run_sweep(device, reps, inj, spec);
+    out["pipe_set"] = pipe_set;
     return out;
 }
 
@@ -878,6 +919,169 @@ py::bytes mfma_raw(int device, const std::string &pipe, py::bytes a_frag,
     HIP_CHECK(hipMemset(d_out.get(), 0xFF, n_out * 4));
     hipLaunchKernelGGL(kernel, dim3(1), dim3(64), 0, 0, d_a.get(), d_b.get(),
                        d_s.get(), d_s.get() + cusweepx::kLanes, d_out.get());
+    HIP_CHECK(hipGetLastError());
+    std::vector<uint32_t> h(n_out);
+    HIP_CHECK(hipMemcpy(h.data(), d_out.get(), n_out * 4, hipMemcpyDeviceToHost));
+    return py::bytes((const char *)h.data(), n_out * 4);
+}
+
+// ---------------- VALU sweep ----------------
+
+// Rounds a VALU sweep launch runs when the caller passes reps = 0, per set
+// (valusweep::Set), chosen from profiles/valu_sweep_mi355x.md as the CU
+// sweep's were: reps = 1 already reached all 1024 SIMDs in one launch every
+// time, so coverage asks for no more; 8 runs every op 8 times on every SIMD
+// and keeps the six sets together under a tenth of the plain probe.
+constexpr int kValuDefaultReps[valusweep::kSets] = {8, 8, 8, 8, 8, 8};
+
+int valu_set_of(const std::string &name) {
+    for (int s = 0; s < valusweep::kSets; ++s)
+        if (name == valusweep::kSetName[s]) return s;
+    throw std::invalid_argument(
+        "op_set must be fma, int, cvt, xlane, salu or trans, not " + name);
+}
+
+const std::vector<uint8_t> &valu_table(int set) {
+    // built on a set's first use (under the GIL)
+    static std::vector<uint8_t> tables[valusweep::kSets];
+    if (tables[set].empty()) tables[set] = valusweep::build_table(set);
+    return tables[set];
+}
+
+template <int... S>
+SweepKernel valu_kernel_of(int set, std::integer_sequence<int, S...>) {
+    static const SweepKernel kernels[] = {valu_sweep_kernel<S>...};
+    return kernels[set];
+}
+
+// Known-answer vector, conversion, cross-lane, scalar and transcendental
+// ops on every SIMD of every CU (valu_sweep_kernel, run_sweep): the dict of
+// cu_sweep with `ops` and `op_set` in the place of `pipes` and `pipe_set`.
+// inject = (block, wave, op) simulates one bad op.
+py::dict valu_sweep(int device, int reps, py::object inject,
+                    const std::string &op_set) {
+    const int set = valu_set_of(op_set);
+    int inj[3];
+    parse_sweep_inject(inject, valusweep::n_ops(set), "op", inj);
+    reps = checked_sweep_reps(reps, kValuDefaultReps[set]);
+    const SweepSpec spec = {
+        valu_kernel_of(set, std::make_integer_sequence<int, valusweep::kSets>{}),
+        &valu_table(set), valusweep::lds_bytes(set), valusweep::n_ops(set),
+        [](int s, int op) { return valusweep::desc(s, op).name; }, set, "op", "ops"};
+    py::dict out = run_sweep(device, reps, inj, spec);
+    out["op_set"] = op_set;
+    return out;
+}
+
+// The VALU sweep's tables for the tests: the packed table, and per op its
+// descriptor and each test's place.  No HIP call, works without a GPU.
+py::dict valu_sweep_reference(const std::string &op_set) {
+    const int set = valu_set_of(op_set);
+    py::list ops;
+    for (int op = 0; op < valusweep::n_ops(set); ++op) {
+        const valusweep::OpDesc &d = valusweep::desc(set, op);
+        py::dict o;
+        o["name"] = d.name;
+        o["mnemonic"] = d.mnemonic;
+        o["widths"] = py::make_tuple(d.w[0], d.w[1], d.w[2], d.w[3]);
+        o["in_words"] = valusweep::in_words(set, op);
+        o["regs"] = (int)d.regs;
+        o["vary"] = py::make_tuple(d.vary[0], d.vary[1], d.vary[2], d.vary[3]);
+        o["out_vary"] = py::make_tuple(d.out_vary[0], d.out_vary[1], d.out_vary[2],
+                                       d.out_vary[3]);
+        py::list offsets;
+        for (int t = 0; t < valusweep::n_tests(set); ++t)
+            offsets.append(valusweep::test_offset(set, op, t));
+        o["offsets"] = offsets;
+        ops.append(o);
+    }
+    const std::vector<uint8_t> &table = valu_table(set);
+    py::dict out;
+    out["op_set"] = op_set;
+    out["ops"] = ops;
+    out["tests_per_op"] = valusweep::n_tests(set);
+    out["lanes"] = valusweep::lanes(set);
+    out["table_bytes"] = valusweep::table_bytes(set);
+    out["lds_bytes"] = valusweep::lds_bytes(set);
+    out["table"] = py::bytes((const char *)table.data(), table.size());
+    out["default_reps"] = kValuDefaultReps[set];
+    out["inject"] = py::make_tuple(kSweepInjectLane, kSweepInjectReg, kSweepInjectBit);
+    return out;
+}
+
+using ValuRawKernel = void (*)(const uint32_t *, uint32_t *);
+
+template <int SET, int... OP>
+ValuRawKernel valu_raw_kernel_of_op(int op, std::integer_sequence<int, OP...>) {
+    static const ValuRawKernel kernels[] = {valu_raw_kernel<SET, OP>...};
+    return kernels[op];
+}
+
+template <int... S>
+ValuRawKernel valu_raw_kernel_of(int set, int op, std::integer_sequence<int, S...>) {
+    ValuRawKernel out = nullptr;
+    auto take = [&](auto which) {
+        constexpr int Q = decltype(which)::value;
+        if (set == Q)
+            out = valu_raw_kernel_of_op<Q>(
+                op, std::make_integer_sequence<int, valusweep::n_ops(Q)>{});
+    };
+    (take(std::integral_constant<int, S>{}), ...);
+    return out;
+}
+
+// One wave of one op of any set on caller-supplied operand words: a, b, c
+// and old are 64 lanes x the descriptor's width of uint32 each, None where
+// the op takes none (the scalar ops and the lane selects read lane 0); the
+// raw result registers, out[lane * regs + r] uint32.  The study and test
+// tool, the counterpart of mfma_raw.  Names and lengths are checked before
+// any HIP call.
+py::bytes valu_raw(int device, const std::string &op_name, py::object a,
+                   py::object b, py::object c, py::object old) {
+    int set = -1, op = -1;
+    for (int s = 0; s < valusweep::kSets; ++s)
+        for (int q = 0; q < valusweep::n_ops(s); ++q)
+            if (op_name == valusweep::desc(s, q).name) {
+                set = s;
+                op = q;
+            }
+    if (set < 0) throw std::invalid_argument("valu_raw: unknown op " + op_name);
+    const valusweep::OpDesc &d = valusweep::desc(set, op);
+    const int NI = valusweep::in_words(set, op);
+    std::vector<uint32_t> in((size_t)valusweep::kLanes * NI);
+    const py::object *given[4] = {&a, &b, &c, &old};
+    const char *const label[4] = {"a", "b", "c", "old"};
+    for (int which = 0; which < 4; ++which) {
+        const int w = d.w[which], at = valusweep::in_offset(set, op, which);
+        if (given[which]->is_none()) {
+            if (w)
+                throw std::invalid_argument("valu_raw: " + op_name + " takes " + label[which]);
+            continue;
+        }
+        if (!w)
+            throw std::invalid_argument("valu_raw: " + op_name + " takes no " + label[which]);
+        if (!py::isinstance<py::bytes>(*given[which]))
+            throw std::invalid_argument(std::string("valu_raw: ") + label[which] +
+                                        " must be bytes");
+        const std::string raw = given[which]->cast<py::bytes>();
+        if (raw.size() != (size_t)valusweep::kLanes * w * 4)
+            throw std::invalid_argument(
+                "valu_raw: " + std::string(label[which]) + " of " + op_name + " is 64 lanes x " +
+                std::to_string(w) + " words, " + std::to_string(valusweep::kLanes * w * 4) +
+                " bytes");
+        for (int l = 0; l < valusweep::kLanes; ++l)
+            std::memcpy(&in[(size_t)l * NI + at], raw.data() + (size_t)l * w * 4, (size_t)w * 4);
+    }
+    ValuRawKernel kernel = valu_raw_kernel_of(
+        set, op, std::make_integer_sequence<int, valusweep::kSets>{});
+
+    HIP_CHECK(hipSetDevice(device));
+    DeviceBuffer<uint32_t> d_in(in.size());
+    HIP_CHECK(hipMemcpy(d_in.get(), in.data(), in.size() * 4, hipMemcpyHostToDevice));
+    const size_t n_out = (size_t)valusweep::kLanes * d.regs;
+    DeviceBuffer<uint32_t> d_out(n_out);
+    HIP_CHECK(hipMemset(d_out.get(), 0xFF, n_out * 4));
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(64), 0, 0, d_in.get(), d_out.get());
     HIP_CHECK(hipGetLastError());
     std::vector<uint32_t> h(n_out);
     HIP_CHECK(hipMemcpy(h.data(), d_out.get(), n_out * 4, hipMemcpyDeviceToHost));
@@ -1769,6 +1973,12 @@ PYBIND11_MODULE(_healthprobe, m) {
           py::arg("a_frag"), py::arg("b_frag"), py::arg("scale_a") = py::none(),
           py::arg("scale_b") = py::none(),
           py::arg("sel") = std::pair<int, int>(0, 0));
+    m.def("valu_sweep", &valu_sweep, py::arg("device") = 0, py::arg("reps") = 0,
+          py::arg("inject") = py::none(), py::arg("op_set") = "fma");
+    m.def("valu_sweep_reference", &valu_sweep_reference, py::arg("op_set") = "fma");
+    m.def("valu_raw", &valu_raw, py::arg("device"), py::arg("op"), py::arg("a"),
+          py::arg("b") = py::none(), py::arg("c") = py::none(),
+          py::arg("old") = py::none());
     m.def("decode_hw_id", &decode_hw_id_py, py::arg("hw_id"),
           py::arg("xcc_id"));
     m.def("hbm_scrub", &hbm_scrub, py::arg("device") = 0,

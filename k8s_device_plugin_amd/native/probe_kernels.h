@@ -576,6 +576,45 @@ struct SweepWaveState {
     bool have_first = false;
 };
 
+// Compares this lane's R result registers d of test t of unit `unit` (a pipe
+// of the CU sweep, an op of the VALU sweep) with want, bit for bit, after the
+// inject hook has flipped its one bit of register inject_reg of one lane;
+// folds the outcome into the wave's state and, for the wave's first failure,
+// lets the lowest bad lane report its registers.
+template <int R>
+__device__ inline void sweep_check(int unit, int t, int lane, uint32_t *d,
+                                   const uint32_t *want, bool inject,
+                                   int inject_reg, SweepWaveState &st,
+                                   SweepRecord *rec) {
+    if (inject && lane == kSweepInjectLane) d[inject_reg] ^= kSweepInjectBit;
+    int bad_reg = -1;  // the lowest mismatching register of this lane
+    uint32_t got = 0, expected = 0;
+#pragma unroll
+    for (int r = R - 1; r >= 0; --r)
+        if (d[r] != want[r]) {
+            bad_reg = r;
+            got = d[r];
+            expected = want[r];
+        }
+    unsigned long long ballot = __ballot(bad_reg >= 0);
+    if (ballot) {
+        st.fail_pipes |= 1u << unit;
+        st.bad_lanes |= ballot;
+        if (!st.have_first) {
+            st.have_first = true;
+            // the lowest bad lane reports its own registers
+            if (lane == __ffsll((long long)ballot) - 1) {
+                rec->first_pipe = unit;
+                rec->first_t = t;
+                rec->first_lane = lane;
+                rec->first_reg = bad_reg;
+                rec->first_got = got;
+                rec->first_expected = expected;
+            }
+        }
+    }
+}
+
 // test t of pipe P of set SET; SA / SB are that test's byte selects (mx)
 template <int SET, int P, int SA, int SB>
 __device__ inline void sweep_test(const unsigned char *table, int t, int lane,
@@ -596,33 +635,7 @@ __device__ inline void sweep_test(const unsigned char *table, int t, int lane,
     want += lane * R;
     uint32_t d[R];
     set_mfma<SET, P, SA, SB>(a + lane * FA, b + lane * FB, sa, sb, zero, d);
-    if (inject && lane == kSweepInjectLane) d[kSweepInjectReg] ^= kSweepInjectBit;
-    int bad_reg = -1;  // the lowest mismatching register of this lane
-    uint32_t got = 0, expected = 0;
-#pragma unroll
-    for (int r = R - 1; r >= 0; --r)
-        if (d[r] != want[r]) {
-            bad_reg = r;
-            got = d[r];
-            expected = want[r];
-        }
-    unsigned long long ballot = __ballot(bad_reg >= 0);
-    if (ballot) {
-        st.fail_pipes |= 1u << P;
-        st.bad_lanes |= ballot;
-        if (!st.have_first) {
-            st.have_first = true;
-            // the lowest bad lane reports its own registers
-            if (lane == __ffsll((long long)ballot) - 1) {
-                rec->first_pipe = P;
-                rec->first_t = t;
-                rec->first_lane = lane;
-                rec->first_reg = bad_reg;
-                rec->first_got = got;
-                rec->first_expected = expected;
-            }
-        }
-    }
+    sweep_check<R>(P, t, lane, d, want, inject, kSweepInjectReg, st, rec);
 }
 
 // the tests of an mx pipe, unrolled: each has its own byte selects

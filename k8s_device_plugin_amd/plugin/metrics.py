@@ -82,6 +82,17 @@ class _ManagerCollector:
                           sum(inst.plugin._sweep_bad_lds_cus.values()))
         yield bl
 
+        bv = GaugeMetricFamily(
+            "amdgpu_dp_deep_probe_bad_valu_simds",
+            "SIMDs that failed the last deep-probe VALU sweep, summed over "
+            "GPUs (0 while the sweep is off)",
+            labels=["resource"],
+        )
+        for resource, inst in self.manager.plugins.items():
+            bv.add_metric([resource],
+                          sum(inst.plugin._sweep_bad_valu_simds.values()))
+        yield bv
+
         counters = {}
         for resource, inst in self.manager.plugins.items():
             if inst.native:

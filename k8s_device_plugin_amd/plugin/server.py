@@ -62,6 +62,7 @@ class AMDGPUPlugin:
         deep_cu_sweep: bool = False,
         deep_lds_sweep: bool = False,
         deep_cu_sweep_extra=(),
+        deep_valu_sweep=(),
     ):
         self.resource = resource
         self.cdi_enabled = cdi_enabled
@@ -94,6 +95,11 @@ class AMDGPUPlugin:
         # every ordinal; independent of the CU sweep
         self.deep_lds_sweep = deep_lds_sweep
         self._sweep_bad_lds_cus: Dict[str, int] = {}  # dev_id -> last count
+        # likewise the known-answer sweep of these VALU op sets ("fma", "int",
+        # "cvt", "xlane", "salu", "trans"), on every ordinal; independent of
+        # the other sweeps.  _sweep_bad_valu_simds counts distinct SIMDs.
+        self.deep_valu_sweep = tuple(deep_valu_sweep)
+        self._sweep_bad_valu_simds: Dict[str, int] = {}  # dev_id -> last count
         self.dev_root = dev_root
         self.paths = paths
         self.devices: Dict[str, GPUDevice] = {}
@@ -215,14 +221,17 @@ class AMDGPUPlugin:
 
     def _deep_probe(self, dev: GPUDevice) -> dict:
         """The deep probe of one physical GPU: MFMA/LDS/HBM with floors on
-        its first HIP ordinal and, with deep_cu_sweep and / or
-        deep_lds_sweep, that sweep on every ordinal, its bad-SIMD or bad-CU
-        lines merged into floor_violations."""
+        its first HIP ordinal and, with deep_cu_sweep, deep_lds_sweep and /
+        or deep_valu_sweep, that sweep on every ordinal, its bad-SIMD or
+        bad-CU lines merged into floor_violations."""
         from ..native import (
             cu_sweep_violations,
             deep_health_probe,
             lds_sweep_with_ecc,
             run_cu_sweep,
+            run_valu_sweep,
+            valu_sweep_incomplete_warning,
+            valu_sweep_violations,
         )
 
         # hbm_scrub_bytes=0: never the HBM scrub here, whatever
@@ -236,6 +245,8 @@ class AMDGPUPlugin:
             sweeps["cu_sweep"] = False
         if self.deep_lds_sweep:
             sweeps["lds_sweep"] = False
+        if self.deep_valu_sweep:
+            sweeps["valu_sweep"] = False
         res = deep_health_probe(device=ordinals[0], hbm_scrub_bytes=0, **sweeps)
         if self.deep_cu_sweep:
             res["cu_sweep"] = {}
@@ -285,6 +296,27 @@ class AMDGPUPlugin:
                                 dev.dev_id, line, ordinal)
             self._sweep_bad_lds_cus[dev.dev_id] = bad_cus
             if unhealthy:
+                res["healthy"] = False
+        if self.deep_valu_sweep:
+            res["valu_sweep"] = {s: {} for s in self.deep_valu_sweep}
+            bad_simds = set()  # a SIMD that fails in two sets counts once
+            for ordinal in ordinals:
+                for op_set in self.deep_valu_sweep:
+                    sweep = run_valu_sweep(ordinal, op_set=op_set)
+                    res["valu_sweep"][op_set][ordinal] = sweep
+                    for b in sweep.get("bad", []):
+                        bad_simds.add((ordinal, b["xcc"], b["se"], b["sh"],
+                                       b["cu"], b["simd"]))
+                    for line in valu_sweep_violations(sweep, op_set):
+                        line = f"{line} (hip device {ordinal})"
+                        log.error("deep probe on %s: %s", dev.dev_id, line)
+                        res["floor_violations"].append(line)
+                    warning = valu_sweep_incomplete_warning(sweep, op_set)
+                    if warning:
+                        log.warning("deep probe on %s: %s (hip device %d)",
+                                    dev.dev_id, warning, ordinal)
+            self._sweep_bad_valu_simds[dev.dev_id] = len(bad_simds)
+            if bad_simds:
                 res["healthy"] = False
         return res
 
