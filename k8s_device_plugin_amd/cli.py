@@ -31,6 +31,9 @@ def _setup_logging(verbose: int) -> None:
 
 
 def device_plugin_main(argv=None) -> int:
+    from .native import (CU_SWEEP, VALU_SWEEP, cu_sweep_extra_sets,
+                         valu_sweep_sets)
+
     ap = argparse.ArgumentParser(
         prog="amd-device-plugin",
         description=f"AMD GPU device plugin for Kubernetes (MI355X-native) v{__version__}",
@@ -70,7 +73,7 @@ def device_plugin_main(argv=None) -> int:
                          "SIMD of every CU, on every HIP device of the GPU, "
                          "and pin a GPU with a bad SIMD Unhealthy")
     ap.add_argument("--deep-probe-cu-sweep-extra", default="",
-                    metavar="mx,wide|all",
+                    metavar=",".join(CU_SWEEP.sets) + "|all",
                     help="with --deep-probe-cu-sweep: sweep these extra pipe "
                          "sets too, wherever the base sweep runs: mx "
                          "(block-scaled fp4 / fp6 with live scales), wide "
@@ -81,7 +84,7 @@ def device_plugin_main(argv=None) -> int:
                          "route into it, on every HIP device of the GPU, and "
                          "pin a GPU with a bad CU Unhealthy")
     ap.add_argument("--deep-probe-valu-sweep", nargs="?", const="all", default="",
-                    metavar="fma,int,cvt,xlane,salu,trans|all",
+                    metavar=",".join(VALU_SWEEP.sets) + "|all",
                     help="with --deep-probe-every / --prestart-deep: also "
                          "run known-answer vector, conversion, cross-lane, "
                          "scalar and transcendental ops on every SIMD of "
@@ -104,8 +107,6 @@ def device_plugin_main(argv=None) -> int:
                          "behavior); default is in-process re-registration")
     ap.add_argument("-v", "--verbose", action="count", default=0)
     args = ap.parse_args(argv)
-    from .native import cu_sweep_extra_sets, valu_sweep_sets
-
     try:
         sweep_extra = cu_sweep_extra_sets(args.deep_probe_cu_sweep_extra)
     except ValueError as e:

@@ -10,7 +10,8 @@ from __future__ import annotations
 
 import importlib
 import os
-from typing import Optional
+from dataclasses import dataclass
+from typing import Callable, Optional
 
 _DIR = os.path.dirname(os.path.abspath(__file__))
 
@@ -96,16 +97,6 @@ def _floor_from_env(env: str, default: float) -> float:
 
 CU_SWEEP_ENV = "AMDXDP_CU_SWEEP"
 CU_SWEEP_INJECT_ENV = "AMDXDP_CU_SWEEP_INJECT"
-
-
-def cu_sweep_enabled(cu_sweep: Optional[bool] = None) -> bool:
-    """An explicit argument wins; None reads AMDXDP_CU_SWEEP (unset, empty
-    or 0 = off)."""
-    if cu_sweep is not None:
-        return bool(cu_sweep)
-    return os.environ.get(CU_SWEEP_ENV, "0").strip() not in ("", "0")
-
-
 CU_SWEEP_EXTRA_ENV = "AMDXDP_CU_SWEEP_EXTRA"
 # The pipes of each set, in the order of native/sweep_table.h and
 # native/sweep_table_ext.h: an injection by name finds its set and index here.
@@ -116,134 +107,63 @@ CU_SWEEP_PIPES = {
 }
 CU_SWEEP_EXTRA_SETS = ("mx", "wide")
 
-
-def cu_sweep_extra_sets(cu_sweep_extra=None) -> tuple:
-    """The extra pipe sets to sweep, in the order mx, wide.  An explicit
-    argument wins: "all", a comma list or an iterable of set names; None
-    reads AMDXDP_CU_SWEEP_EXTRA (unset or empty = none)."""
-    spec = cu_sweep_extra
-    if spec is None:
-        spec = os.environ.get(CU_SWEEP_EXTRA_ENV, "")
-    if isinstance(spec, str):
-        spec = [s.strip() for s in spec.split(",") if s.strip()]
-    names = [str(s).strip().lower() for s in spec]
-    if "all" in names:
-        if len(names) != 1:
-            raise ValueError("cu_sweep_extra: all stands alone")
-        return CU_SWEEP_EXTRA_SETS
-    for name in names:
-        if name not in CU_SWEEP_EXTRA_SETS:
-            raise ValueError(
-                f"cu_sweep_extra: unknown pipe set {name!r}, expected all or "
-                "some of " + ", ".join(CU_SWEEP_EXTRA_SETS))
-    return tuple(s for s in CU_SWEEP_EXTRA_SETS if s in names)
-
-
-def _sweep_inject_from_env(pipe_set: str = "base"):
-    """AMDXDP_CU_SWEEP_INJECT="block:wave:pipe" -> (block, wave, pipe) for
-    the set that owns the pipe, None for every other set: the sweep then
-    simulates one bad matrix pipe on healthy hardware.  pipe is an index
-    into the base set or the name of a pipe of any set."""
-    spec = os.environ.get(CU_SWEEP_INJECT_ENV, "").strip()
-    if not spec:
-        return None
-    fields = spec.split(":")
-    try:
-        block, wave = (int(x) for x in fields[:2])
-        if len(fields) != 3:
-            raise ValueError
-        try:
-            owner, pipe = "base", int(fields[2])
-        except ValueError:
-            name = fields[2].strip()
-            owner = next(s for s, pipes in CU_SWEEP_PIPES.items()
-                         if name in pipes)
-            pipe = CU_SWEEP_PIPES[owner].index(name)
-    except (ValueError, StopIteration):
-        raise ValueError(
-            f"{CU_SWEEP_INJECT_ENV}={spec!r}: expected block:wave:pipe, pipe "
-            "an index into the base set or a pipe's name"
-        ) from None
-    return (block, wave, pipe) if owner == pipe_set else None
-
-
-def cu_sweep_violations(sweep: dict) -> list:
-    """One line per SIMD that failed the sweep."""
-    return [
-        "cu_sweep: xcc {xcc} se {se} cu {cu} simd {simd} failed {pipes}".format(
-            xcc=b["xcc"], se=b["se"], cu=b["cu"], simd=b["simd"],
-            pipes=",".join(b["pipes"]),
-        )
-        for b in sweep.get("bad", [])
-    ]
-
-
-def run_cu_sweep(device: int = 0, mod=None, pipe_set: str = "base") -> dict:
-    """Known-answer MFMA sweep of every CU and SIMD of one HIP device, over
-    the base pipes or one of the extra sets (CU_SWEEP_EXTRA_SETS)."""
-    if mod is None:
-        mod = load_healthprobe(required=True)
-    inject = _sweep_inject_from_env(pipe_set)
-    if pipe_set == "base":
-        return mod.cu_sweep(device=device, inject=inject)
-    return mod.cu_sweep(device=device, inject=inject, pipe_set=pipe_set)
-
-
-def cu_sweep_incomplete_warning(sweep: dict, pipe_set: str = "base"):
-    """The warning line of a sweep that found nothing bad but could not reach
-    every SIMD, or None."""
-    if not sweep.get("ok") or sweep.get("coverage_complete"):
-        return None
-    tag = "" if pipe_set == "base" else f"[{pipe_set}]"
-    return "cu_sweep_incomplete{}: {} of {} CUs, {} SIMDs".format(
-        tag, sweep.get("cus_covered"), sweep.get("cu_count"),
-        sweep.get("simds_covered"))
-
+LDS_SWEEP_ENV = "AMDXDP_LDS_SWEEP"
+LDS_SWEEP_INJECT_ENV = "AMDXDP_LDS_SWEEP_INJECT"
 
 VALU_SWEEP_ENV = "AMDXDP_VALU_SWEEP"
 VALU_SWEEP_INJECT_ENV = "AMDXDP_VALU_SWEEP_INJECT"
 # the op sets of native/valu_table.h, in its order
 VALU_SWEEP_SETS = ("fma", "int", "cvt", "xlane", "salu", "trans")
 
+HBM_SCRUB_ENV = "AMDXDP_HBM_SCRUB_BYTES"
+HBM_SCRUB_DEFAULT_RESERVE = 2 << 30
+# below this share of the card's VRAM a scrub of "all" says that it was partial
+HBM_SCRUB_FULL_SHARE = 0.9
 
-def valu_sweep_sets(valu_sweep=None) -> tuple:
-    """The VALU op sets to sweep, in the order of VALU_SWEEP_SETS.  An
-    explicit argument wins: False or True (none, all), "all", a comma list or
-    an iterable of set names; None reads AMDXDP_VALU_SWEEP (unset, empty or
-    0 = none, 1 or all = every set, otherwise a comma list)."""
-    spec = valu_sweep
+
+# ---- what the opt-in checks share ----
+
+
+def _switch_from_env(arg: Optional[bool], env: str) -> bool:
+    """An explicit argument wins; None reads env (unset, empty or 0 = off)."""
+    if arg is not None:
+        return bool(arg)
+    return os.environ.get(env, "0").strip() not in ("", "0")
+
+
+def _sets_from(spec, env: str, what: str, noun: str, sets: tuple,
+               switch: bool = False) -> tuple:
+    """The sets that spec names, in the order of `sets`.  An explicit spec
+    wins: "all", a comma list or an iterable of names; None reads env (unset
+    or empty = none).  switch: False / True and "0" / "1" are none / all."""
     if spec is None:
-        spec = os.environ.get(VALU_SWEEP_ENV, "")
-    if spec is False:
-        return ()
-    if spec is True:
-        return VALU_SWEEP_SETS
+        spec = os.environ.get(env, "")
+    if switch and isinstance(spec, bool):
+        return sets if spec else ()
     if isinstance(spec, str):
         spec = [s.strip() for s in spec.split(",") if s.strip()]
     names = [str(s).strip().lower() for s in spec]
-    if names in (["0"], []):
+    if switch and names == ["0"]:
         return ()
-    if "all" in names or "1" in names:
+    if "all" in names or (switch and "1" in names):
         if len(names) != 1:
-            raise ValueError("valu_sweep: all stands alone")
-        return VALU_SWEEP_SETS
+            raise ValueError(f"{what}: all stands alone")
+        return sets
     for name in names:
-        if name not in VALU_SWEEP_SETS:
+        if name not in sets:
             raise ValueError(
-                f"valu_sweep: unknown op set {name!r}, expected all or "
-                "some of " + ", ".join(VALU_SWEEP_SETS))
-    return tuple(s for s in VALU_SWEEP_SETS if s in names)
+                f"{what}: unknown {noun} {name!r}, expected all or "
+                "some of " + ", ".join(sets))
+    return tuple(s for s in sets if s in names)
 
 
-def _valu_op_names(mod, op_set: str) -> list:
-    return [op["name"] for op in mod.valu_sweep_reference(op_set)["ops"]]
-
-
-def _valu_inject_from_env(mod, op_set: str):
-    """AMDXDP_VALU_SWEEP_INJECT="block:wave:op" -> (block, wave, index) for
-    the set that owns the op, None for every other set: the sweep then
-    simulates one bad op on healthy hardware.  op is the op's name."""
-    spec = os.environ.get(VALU_SWEEP_INJECT_ENV, "").strip()
+def _inject_from_env(env: str, which: str, sets, names_of, expected: str,
+                     index_set: Optional[str] = None):
+    """env="block:wave:unit" -> (block, wave, index) for the set `which` if
+    it owns the unit, None for every other set: the sweep then simulates one
+    bad unit on healthy hardware.  unit is a name out of names_of(set) or,
+    with index_set, an index into that set."""
+    spec = os.environ.get(env, "").strip()
     if not spec:
         return None
     fields = spec.split(":")
@@ -251,65 +171,236 @@ def _valu_inject_from_env(mod, op_set: str):
         if len(fields) != 3:
             raise ValueError
         block, wave = (int(x) for x in fields[:2])
-        name = fields[2].strip()
-        owner = next(s for s in VALU_SWEEP_SETS
-                     if name in _valu_op_names(mod, s))
+        unit = fields[2].strip()
+        try:
+            if index_set is None:
+                raise ValueError
+            owner, index = index_set, int(unit)
+        except ValueError:
+            owner = next(s for s in sets if unit in names_of(s))
+            index = list(names_of(owner)).index(unit)
     except (ValueError, StopIteration):
-        raise ValueError(
-            f"{VALU_SWEEP_INJECT_ENV}={spec!r}: expected block:wave:op, op "
-            "the name of an op of one of the sets"
-        ) from None
-    if owner != op_set:
-        return None
-    return (block, wave, _valu_op_names(mod, owner).index(name))
+        raise ValueError(f"{env}={spec!r}: expected {expected}") from None
+    return (block, wave, index) if owner == which else None
 
 
-def run_valu_sweep(device: int = 0, mod=None, op_set: str = "fma") -> dict:
-    """Known-answer sweep of one VALU op set (VALU_SWEEP_SETS) over every CU
-    and SIMD of one HIP device."""
-    if mod is None:
-        mod = load_healthprobe(required=True)
-    inject = _valu_inject_from_env(mod, op_set)
-    return mod.valu_sweep(device=device, inject=inject, op_set=op_set)
-
-
-def valu_sweep_violations(sweep: dict, op_set: str = "") -> list:
-    """One line per SIMD that failed the sweep of one set.  The scalar unit
-    belongs to the CU: for set salu the SIMD is only where it was seen."""
+def _simd_violations(key: str, sweep: dict, failed: str, sep: str,
+                     scalar: bool = False) -> list:
+    """One line per bad SIMD of a known-answer sweep.  scalar: the unit
+    belongs to the CU, the SIMD is only where it was seen."""
     lines = []
     for b in sweep.get("bad", []):
-        ops = ", ".join(b["ops"])
-        if op_set == "salu":
-            lines.append(
-                "valu_sweep: xcc {} se {} cu {} scalar unit failed {} "
-                "(seen by simd {})".format(b["xcc"], b["se"], b["cu"], ops,
-                                           b["simd"]))
+        where = "{}: xcc {} se {} cu {}".format(key, b["xcc"], b["se"], b["cu"])
+        names = sep.join(b[failed])
+        if scalar:
+            lines.append(f"{where} scalar unit failed {names} "
+                         f"(seen by simd {b['simd']})")
         else:
-            lines.append("valu_sweep: xcc {} se {} cu {} simd {} failed {}".format(
-                b["xcc"], b["se"], b["cu"], b["simd"], ops))
+            lines.append(f"{where} simd {b['simd']} failed {names}")
     return lines
 
 
-def valu_sweep_incomplete_warning(sweep: dict, op_set: str):
-    """The warning line of a set's sweep that found nothing bad but could
-    not reach every SIMD, or None."""
+def _incomplete_warning(key: str, sweep: dict, which: Optional[str] = None,
+                        simds: bool = True):
+    """The warning line of a sweep that found nothing bad but could not reach
+    every CU (and SIMD), or None."""
     if not sweep.get("ok") or sweep.get("coverage_complete"):
         return None
-    return "valu_sweep_incomplete[{}]: {} of {} CUs, {} SIMDs".format(
-        op_set, sweep.get("cus_covered"), sweep.get("cu_count"),
-        sweep.get("simds_covered"))
+    line = "{}_incomplete{}: {} of {} CUs".format(
+        key, f"[{which}]" if which else "", sweep.get("cus_covered"),
+        sweep.get("cu_count"))
+    if simds:
+        line += ", {} SIMDs".format(sweep.get("simds_covered"))
+    return line
 
 
-LDS_SWEEP_ENV = "AMDXDP_LDS_SWEEP"
-LDS_SWEEP_INJECT_ENV = "AMDXDP_LDS_SWEEP_INJECT"
+def read_ecc_counts(bdf: str, sysroot: str = "/", block: str = "umc"):
+    """{"ue": n, "ce": n} from <sysroot>/sys/bus/pci/devices/<bdf>/ras/
+    <block>_err_count (lines of `key: integer`, other keys ignored), or None
+    when the file cannot be read or does not hold both.  block: "umc" is the
+    HBM's counters, "gfx" those of the compute units, LDS included."""
+    path = os.path.join(sysroot, "sys/bus/pci/devices", bdf, "ras",
+                        f"{block}_err_count")
+    counts = {}
+    try:
+        with open(path) as f:
+            for line in f:
+                key, sep, value = line.partition(":")
+                if sep and key.strip() in ("ue", "ce"):
+                    counts[key.strip()] = int(value.strip(), 0)
+    except (OSError, ValueError):
+        return None
+    return counts if len(counts) == 2 else None
+
+
+def _between_ecc_readings(sweep: "Sweep", run, device: int, mod, sysroot: str):
+    """run() between two readings of the RAS counters that sweep.ecc names.
+    Sets `ecc` on the result (before and after, None when unreadable) and
+    returns (result, violations, warnings): uncorrectable errors during the
+    run are a violation, corrected ones a warning."""
+    block, label, act = sweep.ecc
+    bdf = None
+    try:
+        bdf = mod.pci_bus_ids()[device].lower()
+    except Exception:
+        pass
+    before = read_ecc_counts(bdf, sysroot, block) if bdf else None
+    res = run()
+    after = read_ecc_counts(bdf, sysroot, block) if bdf else None
+    violations, warnings = [], []
+    res["ecc"] = None
+    if before is not None and after is not None:
+        res["ecc"] = {"before": before, "after": after}
+        ue = after["ue"] - before["ue"]
+        ce = after["ce"] - before["ce"]
+        if ue > 0:
+            violations.append(f"{sweep.key}: {ue} uncorrectable {label}ECC "
+                              f"errors during the {act}")
+        if ce > 0:
+            warnings.append(f"{sweep.key}_ecc: {ce} corrected {label}ECC "
+                            f"errors during the {act}")
+    return res, violations, warnings
+
+
+@dataclass(frozen=True)
+class Sweep:
+    """One opt-in check of the deep probe.  `which` is one of the sets that
+    select() returned: a set's name, or None for a sweep without sets and for
+    the CU sweep's base set."""
+
+    key: str                     # result key and prefix of its lines
+    envs: tuple                  # the switch, then what chooses sets or injects
+    select: Callable             # argument (None = env) -> the sets to run
+    run: Callable = None         # (device, mod, which) -> result
+    violations: Callable = None  # (result, which) -> lines
+    incomplete: Callable = None  # (result, which) -> warning line or None
+    sets: tuple = ()             # the set names select() accepts
+    sets_key: str = None         # a named set's result goes here, {set: result}
+    ecc: tuple = None            # RAS counters read before and after: (block,
+    #                              its name in the lines, what ran)
+    counts: str = None           # the plugin's bad-count gauge: distinct
+    #                              "simds" over all sets, or "cus" summed
+    # (result, which, ordinal) -> the plugin's own wording of the incomplete
+    # line, where it does not log that line itself
+    plugin_incomplete: Callable = None
+    # (device, mod, which) -> (result, violations, warnings): a policy of its
+    # own in place of check_sweep's
+    check: Callable = None
+
+    def place(self, res: dict, which, result: dict, ordinal=None) -> None:
+        """Files a result under key, a named set's under sets_key as
+        {set: result}; with an ordinal (the plugin) one level further down,
+        as {ordinal: result}."""
+        at, name = res, self.key
+        if which is not None and self.sets_key:
+            at, name = res.setdefault(self.sets_key, {}), which
+        if ordinal is None:
+            at[name] = result
+        else:
+            at.setdefault(name, {})[ordinal] = result
+
+
+def check_sweep(sweep: Sweep, device: int = 0, which=None, mod=None,
+                sysroot: str = "/"):
+    """One run of a sweep on one HIP device -> (result, violation lines,
+    warning lines).  A sweep with `ecc` runs between two readings of those
+    RAS counters, and its result carries `ecc`, `violations` and `warnings`."""
+    if mod is None:
+        mod = load_healthprobe(required=True)
+    if sweep.check:
+        return sweep.check(device, mod, which)
+
+    def run():
+        return sweep.run(device, mod, which)
+    res, ecc_violations, ecc_warnings = (
+        _between_ecc_readings(sweep, run, device, mod, sysroot) if sweep.ecc
+        else (run(), [], []))
+    violations = sweep.violations(res, which) + ecc_violations
+    warning = sweep.incomplete(res, which)
+    warnings = ([warning] if warning else []) + ecc_warnings
+    if sweep.ecc:
+        res["violations"] = violations
+        res["warnings"] = warnings
+    return res, violations, warnings
+
+
+# ---- CU sweep ----
+
+
+def cu_sweep_enabled(cu_sweep: Optional[bool] = None) -> bool:
+    """An explicit argument wins; None reads AMDXDP_CU_SWEEP (unset, empty
+    or 0 = off)."""
+    return _switch_from_env(cu_sweep, CU_SWEEP_ENV)
+
+
+def cu_sweep_extra_sets(cu_sweep_extra=None) -> tuple:
+    """The extra pipe sets to sweep, in the order mx, wide.  An explicit
+    argument wins: "all", a comma list or an iterable of set names; None
+    reads AMDXDP_CU_SWEEP_EXTRA (unset or empty = none)."""
+    return _sets_from(cu_sweep_extra, CU_SWEEP_EXTRA_ENV, "cu_sweep_extra",
+                      "pipe set", CU_SWEEP_EXTRA_SETS)
+
+
+def _cu_sweep_select(arg) -> tuple:
+    """(cu_sweep, cu_sweep_extra) -> None for the base set, then the extra
+    sets; the extra sets act only while the sweep itself is on."""
+    cu_sweep, extra = arg
+    if not cu_sweep_enabled(cu_sweep):
+        return ()
+    return (None,) + cu_sweep_extra_sets(extra)
+
+
+def run_cu_sweep(device: int = 0, mod=None, pipe_set: str = "base") -> dict:
+    """Known-answer MFMA sweep of every CU and SIMD of one HIP device, over
+    the base pipes or one of the extra sets (CU_SWEEP_EXTRA_SETS).
+    AMDXDP_CU_SWEEP_INJECT="block:wave:pipe" simulates one bad matrix pipe:
+    pipe is an index into the base set or the name of a pipe of any set."""
+    if mod is None:
+        mod = load_healthprobe(required=True)
+    inject = _inject_from_env(
+        CU_SWEEP_INJECT_ENV, pipe_set, CU_SWEEP_PIPES, CU_SWEEP_PIPES.get,
+        "block:wave:pipe, pipe an index into the base set or a pipe's name",
+        index_set="base")
+    if pipe_set == "base":  # a module from before the extra sets has no such
+        return mod.cu_sweep(device=device, inject=inject)  # parameter
+    return mod.cu_sweep(device=device, inject=inject, pipe_set=pipe_set)
+
+
+def cu_sweep_violations(sweep: dict) -> list:
+    """One line per SIMD that failed the sweep."""
+    return _simd_violations("cu_sweep", sweep, "pipes", ",")
+
+
+def cu_sweep_incomplete_warning(sweep: dict, pipe_set: str = "base"):
+    """The warning line of a sweep that found nothing bad but could not reach
+    every SIMD, or None."""
+    return _incomplete_warning("cu_sweep", sweep,
+                               None if pipe_set == "base" else pipe_set)
+
+
+CU_SWEEP = Sweep(
+    key="cu_sweep",
+    envs=(CU_SWEEP_ENV, CU_SWEEP_EXTRA_ENV, CU_SWEEP_INJECT_ENV),
+    sets=CU_SWEEP_EXTRA_SETS, sets_key="cu_sweep_extra", counts="simds",
+    select=_cu_sweep_select,
+    run=lambda device, mod, which: run_cu_sweep(device, mod, which or "base"),
+    violations=lambda sweep, which: cu_sweep_violations(sweep),
+    incomplete=lambda sweep, which: cu_sweep_incomplete_warning(
+        sweep, which or "base"),
+    plugin_incomplete=lambda sweep, which, ordinal: (
+        "cu_sweep ({} pipes) reached {} of {} CUs on hip device {}".format(
+            which or "base", sweep.get("cus_covered"), sweep.get("cu_count"),
+            ordinal)),
+)
+
+
+# ---- LDS sweep ----
 
 
 def lds_sweep_enabled(lds_sweep: Optional[bool] = None) -> bool:
     """An explicit argument wins; None reads AMDXDP_LDS_SWEEP (unset, empty
     or 0 = off)."""
-    if lds_sweep is not None:
-        return bool(lds_sweep)
-    return os.environ.get(LDS_SWEEP_ENV, "0").strip() not in ("", "0")
+    return _switch_from_env(lds_sweep, LDS_SWEEP_ENV)
 
 
 def _lds_inject_from_env():
@@ -326,6 +417,13 @@ def _lds_inject_from_env():
             f"{LDS_SWEEP_INJECT_ENV}={spec!r}: expected block:element:word:bit"
         ) from None
     return (block, "b128", "address", 0, "flip", element, word, bit)
+
+
+def run_lds_sweep(device: int = 0, mod=None) -> dict:
+    """March test of the whole LDS of every CU of one HIP device."""
+    if mod is None:
+        mod = load_healthprobe(required=True)
+    return mod.lds_sweep(device=device, corrupt=_lds_inject_from_env())
 
 
 def lds_sweep_violations(sweep: dict) -> list:
@@ -345,17 +443,76 @@ def lds_sweep_violations(sweep: dict) -> list:
     return lines
 
 
-def run_lds_sweep(device: int = 0, mod=None) -> dict:
-    """March test of the whole LDS of every CU of one HIP device."""
+LDS_SWEEP = Sweep(
+    key="lds_sweep", envs=(LDS_SWEEP_ENV, LDS_SWEEP_INJECT_ENV),
+    ecc=("gfx", "gfx ", "sweep"), counts="cus",
+    select=lambda arg: (None,) if lds_sweep_enabled(arg) else (),
+    run=lambda device, mod, which: run_lds_sweep(device, mod),
+    violations=lambda sweep, which: lds_sweep_violations(sweep),
+    incomplete=lambda sweep, which: _incomplete_warning(
+        "lds_sweep", sweep, simds=False),
+)
+
+
+def lds_sweep_with_ecc(device: int = 0, mod=None, sysroot: str = "/") -> dict:
+    """run_lds_sweep between two readings of the GPU's gfx RAS counters.
+
+    Adds `violations`, `warnings` and `ecc` (gfx_err_count before and after,
+    None when unreadable) to the module's result: LDS is ECC-protected, so a
+    weak cell may show only as a corrected error.
+    """
+    return check_sweep(LDS_SWEEP, device, None, mod, sysroot)[0]
+
+
+# ---- VALU sweep ----
+
+
+def valu_sweep_sets(valu_sweep=None) -> tuple:
+    """The VALU op sets to sweep, in the order of VALU_SWEEP_SETS.  An
+    explicit argument wins: False or True (none, all), "all", a comma list or
+    an iterable of set names; None reads AMDXDP_VALU_SWEEP (unset, empty or
+    0 = none, 1 or all = every set, otherwise a comma list)."""
+    return _sets_from(valu_sweep, VALU_SWEEP_ENV, "valu_sweep", "op set",
+                      VALU_SWEEP_SETS, switch=True)
+
+
+def run_valu_sweep(device: int = 0, mod=None, op_set: str = "fma") -> dict:
+    """Known-answer sweep of one VALU op set (VALU_SWEEP_SETS) over every CU
+    and SIMD of one HIP device.  AMDXDP_VALU_SWEEP_INJECT="block:wave:op"
+    simulates one bad op, named as in the module's tables."""
     if mod is None:
         mod = load_healthprobe(required=True)
-    return mod.lds_sweep(device=device, corrupt=_lds_inject_from_env())
+    inject = _inject_from_env(
+        VALU_SWEEP_INJECT_ENV, op_set, VALU_SWEEP_SETS,
+        lambda s: [op["name"] for op in mod.valu_sweep_reference(s)["ops"]],
+        "block:wave:op, op the name of an op of one of the sets")
+    return mod.valu_sweep(device=device, inject=inject, op_set=op_set)
 
 
-HBM_SCRUB_ENV = "AMDXDP_HBM_SCRUB_BYTES"
-HBM_SCRUB_DEFAULT_RESERVE = 2 << 30
-# below this share of the card's VRAM a scrub of "all" says that it was partial
-HBM_SCRUB_FULL_SHARE = 0.9
+def valu_sweep_violations(sweep: dict, op_set: str = "") -> list:
+    """One line per SIMD that failed the sweep of one set.  The scalar unit
+    belongs to the CU: for set salu the SIMD is only where it was seen."""
+    return _simd_violations("valu_sweep", sweep, "ops", ", ",
+                            scalar=op_set == "salu")
+
+
+def valu_sweep_incomplete_warning(sweep: dict, op_set: str):
+    """The warning line of a set's sweep that found nothing bad but could
+    not reach every SIMD, or None."""
+    return _incomplete_warning("valu_sweep", sweep, op_set)
+
+
+VALU_SWEEP = Sweep(
+    key="valu_sweep", envs=(VALU_SWEEP_ENV, VALU_SWEEP_INJECT_ENV),
+    sets=VALU_SWEEP_SETS, sets_key="valu_sweep", counts="simds",
+    select=valu_sweep_sets,
+    run=lambda device, mod, which: run_valu_sweep(device, mod, which),
+    violations=valu_sweep_violations,
+    incomplete=valu_sweep_incomplete_warning,
+)
+
+
+# ---- HBM scrub ----
 
 
 def hbm_scrub_bytes_from_env(hbm_scrub_bytes=None):
@@ -382,25 +539,6 @@ def hbm_scrub_bytes_from_env(hbm_scrub_bytes=None):
     return spec or None
 
 
-def read_ecc_counts(bdf: str, sysroot: str = "/", block: str = "umc"):
-    """{"ue": n, "ce": n} from <sysroot>/sys/bus/pci/devices/<bdf>/ras/
-    <block>_err_count (lines of `key: integer`, other keys ignored), or None
-    when the file cannot be read or does not hold both.  block: "umc" is the
-    HBM's counters, "gfx" those of the compute units, LDS included."""
-    path = os.path.join(sysroot, "sys/bus/pci/devices", bdf, "ras",
-                        f"{block}_err_count")
-    counts = {}
-    try:
-        with open(path) as f:
-            for line in f:
-                key, sep, value = line.partition(":")
-                if sep and key.strip() in ("ue", "ce"):
-                    counts[key.strip()] = int(value.strip(), 0)
-    except (OSError, ValueError):
-        return None
-    return counts if len(counts) == 2 else None
-
-
 def hbm_scrub_violations(scrub: dict) -> list:
     """One line per bad 2 MiB-aligned range, one for an overwritten guard."""
     lines = []
@@ -416,6 +554,20 @@ def hbm_scrub_violations(scrub: dict) -> list:
     if scrub.get("guard_ok") is False:
         lines.append("hbm_scrub: guard band overwritten")
     return lines
+
+
+def _check_hbm_scrub(device, mod, which):
+    scrub = hbm_scrub(device, which, mod=mod)
+    return scrub, scrub["violations"], scrub["warnings"]
+
+
+# `which` is the byte count or "all"
+HBM_SCRUB = Sweep(
+    key="hbm_scrub", envs=(HBM_SCRUB_ENV,), ecc=("umc", "", "scrub"),
+    select=lambda arg: tuple(
+        b for b in [hbm_scrub_bytes_from_env(arg)] if b is not None),
+    check=_check_hbm_scrub,
+)
 
 
 def hbm_scrub(device: int = 0, bytes=None,
@@ -439,75 +591,26 @@ def hbm_scrub(device: int = 0, bytes=None,
             raise ValueError(
                 f"hbm_scrub: {free} bytes free, reserve_bytes={reserve_bytes}"
                 " leaves nothing to test")
-    bdf = None
-    try:
-        bdf = mod.pci_bus_ids()[device].lower()
-    except Exception:
-        pass
-    ecc_before = read_ecc_counts(bdf, sysroot) if bdf else None
     kwargs = {} if patterns is None else {"patterns": list(patterns)}
-    res = mod.hbm_scrub(device=device, bytes=int(bytes), **kwargs)
-    ecc_after = read_ecc_counts(bdf, sysroot) if bdf else None
-
-    violations = hbm_scrub_violations(res)
+    res, ecc_violations, ecc_warnings = _between_ecc_readings(
+        HBM_SCRUB,
+        lambda: mod.hbm_scrub(device=device, bytes=int(bytes), **kwargs),
+        device, mod, sysroot)
+    violations = hbm_scrub_violations(res) + ecc_violations
     warnings = []
     if whole and res["bytes_tested"] < HBM_SCRUB_FULL_SHARE * res["vram_bytes"]:
         warnings.append("hbm_scrub_partial: tested {} of {} bytes".format(
             res["bytes_tested"], res["vram_bytes"]))
-    res["ecc"] = None
-    if ecc_before is not None and ecc_after is not None:
-        res["ecc"] = {"before": ecc_before, "after": ecc_after}
-        ue = ecc_after["ue"] - ecc_before["ue"]
-        ce = ecc_after["ce"] - ecc_before["ce"]
-        if ue > 0:
-            violations.append(
-                f"hbm_scrub: {ue} uncorrectable ECC errors during the scrub")
-        if ce > 0:
-            warnings.append(
-                f"hbm_scrub_ecc: {ce} corrected ECC errors during the scrub")
     res["violations"] = violations
-    res["warnings"] = warnings
+    res["warnings"] = warnings + ecc_warnings
     res["healthy"] = not violations
     return res
 
 
-def lds_sweep_with_ecc(device: int = 0, mod=None, sysroot: str = "/") -> dict:
-    """run_lds_sweep between two readings of the GPU's gfx RAS counters.
+# ---- the deep probe ----
 
-    Adds `violations`, `warnings` and `ecc` (gfx_err_count before and after,
-    None when unreadable) to the module's result: LDS is ECC-protected, so a
-    weak cell may show only as a corrected error.
-    """
-    if mod is None:
-        mod = load_healthprobe(required=True)
-    bdf = None
-    try:
-        bdf = mod.pci_bus_ids()[device].lower()
-    except Exception:
-        pass
-    ecc_before = read_ecc_counts(bdf, sysroot, "gfx") if bdf else None
-    res = run_lds_sweep(device, mod)
-    ecc_after = read_ecc_counts(bdf, sysroot, "gfx") if bdf else None
-
-    violations = lds_sweep_violations(res)
-    warnings = []
-    if res.get("ok") and not res.get("coverage_complete"):
-        warnings.append("lds_sweep_incomplete: {} of {} CUs".format(
-            res.get("cus_covered"), res.get("cu_count")))
-    res["ecc"] = None
-    if ecc_before is not None and ecc_after is not None:
-        res["ecc"] = {"before": ecc_before, "after": ecc_after}
-        ue = ecc_after["ue"] - ecc_before["ue"]
-        ce = ecc_after["ce"] - ecc_before["ce"]
-        if ue > 0:
-            violations.append(
-                f"lds_sweep: {ue} uncorrectable gfx ECC errors during the sweep")
-        if ce > 0:
-            warnings.append(
-                f"lds_sweep_ecc: {ce} corrected gfx ECC errors during the sweep")
-    res["violations"] = violations
-    res["warnings"] = warnings
-    return res
+# in the order in which deep_health_probe runs them
+SWEEPS = (CU_SWEEP, LDS_SWEEP, VALU_SWEEP, HBM_SCRUB)
 
 
 def deep_health_probe(
@@ -564,9 +667,14 @@ def deep_health_probe(
     if hbm_floor_gbps is None:
         hbm_floor_gbps = _floor_from_env(HBM_FLOOR_ENV,
                                          DEFAULT_HBM_FLOOR_GBPS)
+    # or ValueError, before anything runs (the extra sets also while the CU
+    # sweep is off); what else the environment chooses is read when its
+    # sweep's turn comes
     if cu_sweep_extra is not None:
-        cu_sweep_extra = cu_sweep_extra_sets(cu_sweep_extra)  # or ValueError
-    valu_sets = valu_sweep_sets(valu_sweep)  # or ValueError
+        cu_sweep_extra = cu_sweep_extra_sets(cu_sweep_extra)
+    valu_sweep = valu_sweep_sets(valu_sweep)
+    asked = {"cu_sweep": (cu_sweep, cu_sweep_extra), "lds_sweep": lds_sweep,
+             "valu_sweep": valu_sweep, "hbm_scrub": hbm_scrub_bytes}
     mod = load_healthprobe(required=True)
     res = mod.run_probe(device=device, hbm_bytes=hbm_bytes)
     violations = []
@@ -588,40 +696,17 @@ def deep_health_probe(
         "mfma_tflops": mfma_floor_tflops,
         "hbm_gbps": hbm_floor_gbps,
     }
-    if cu_sweep_enabled(cu_sweep):
-        sweep = run_cu_sweep(device, mod)
-        res["cu_sweep"] = sweep
-        violations.extend(cu_sweep_violations(sweep))
-        warning = cu_sweep_incomplete_warning(sweep)
-        if warning:
-            res["warnings"] = [warning]
-        for pipe_set in cu_sweep_extra_sets(cu_sweep_extra):
-            sweep = run_cu_sweep(device, mod, pipe_set)
-            res.setdefault("cu_sweep_extra", {})[pipe_set] = sweep
-            violations.extend(cu_sweep_violations(sweep))
-            warning = cu_sweep_incomplete_warning(sweep, pipe_set)
-            if warning:
-                res.setdefault("warnings", []).append(warning)
-    if lds_sweep_enabled(lds_sweep):
-        sweep = lds_sweep_with_ecc(device, mod, sysroot)
-        res["lds_sweep"] = sweep
-        violations.extend(sweep["violations"])
-        if sweep["warnings"]:
-            res.setdefault("warnings", []).extend(sweep["warnings"])
-    for op_set in valu_sets:
-        sweep = run_valu_sweep(device, mod, op_set)
-        res.setdefault("valu_sweep", {})[op_set] = sweep
-        violations.extend(valu_sweep_violations(sweep, op_set))
-        warning = valu_sweep_incomplete_warning(sweep, op_set)
-        if warning:
-            res.setdefault("warnings", []).append(warning)
-    scrub_bytes = hbm_scrub_bytes_from_env(hbm_scrub_bytes)
-    if scrub_bytes is not None:
-        scrub = hbm_scrub(device, scrub_bytes, mod=mod)
-        res["hbm_scrub"] = scrub
-        violations.extend(scrub["violations"])
-        if scrub["warnings"]:
-            res.setdefault("warnings", []).extend(scrub["warnings"])
+    warnings = []
+    for sweep in SWEEPS:
+        for which in sweep.select(asked[sweep.key]):
+            # (the scrub reads its counters under /, whatever sysroot says)
+            result, lines, warns = check_sweep(sweep, device, which, mod,
+                                               sysroot)
+            sweep.place(res, which, result)
+            violations.extend(lines)
+            warnings.extend(warns)
+    if warnings:
+        res["warnings"] = warnings
     res["floor_violations"] = violations
     if violations:
         res["healthy"] = False

@@ -273,12 +273,43 @@ constexpr long long kCopyCheckMaxN = 1ll << 32;      // 64 GiB per buffer
 constexpr long long kCopyCheckMaxGuard = 1ll << 20;  // float4s per band
 constexpr long long kCopyCheckMaxData = 1ll << 21;   // n for return_data
 
+// Damage to one 16-byte element of device memory from the host, with
+// hipMemcpy inside the allocation and no kernel: bit `bit` of its 32-bit
+// word `word` flipped or, with alias_of, the whole element := *alias_of.
+void damage_from_host(void *element, long long word, long long bit,
+                      const void *alias_of) {
+    if (alias_of) {
+        HIP_CHECK(hipMemcpy(element, alias_of, 16, hipMemcpyDeviceToDevice));
+        return;
+    }
+    uint32_t *at = static_cast<uint32_t *>(element) + word;
+    uint32_t w = 0;
+    HIP_CHECK(hipMemcpy(&w, at, sizeof(w), hipMemcpyDeviceToHost));
+    w ^= 1u << bit;
+    HIP_CHECK(hipMemcpy(at, &w, sizeof(w), hipMemcpyHostToDevice));
+}
+
+// Whether both guard bands of a guard + data + guard allocation still hold
+// the poison.
+bool guards_hold_poison(const void *alloc, size_t guard_bytes, size_t data_bytes) {
+    bool ok = true;
+    std::vector<unsigned char> band(guard_bytes);
+    const char *low = static_cast<const char *>(alloc);
+    for (const char *from : {low, low + guard_bytes + data_bytes}) {
+        if (band.empty()) break;
+        HIP_CHECK(hipMemcpy(band.data(), from, band.size(),
+                            hipMemcpyDeviceToHost));
+        for (unsigned char b : band)
+            if (b != hbmpattern::kPoisonByte) ok = false;
+    }
+    return ok;
+}
+
 // ONE hbm_copy_kernel launch of n float4s into the middle of a poisoned
 // guard + n + guard allocation (guard counts float4s), then the device
 // verifier over the n elements and a host check that both guard bands still
 // hold the poison.  blocks = 0 takes the production grid, hbm_copy_blocks.
-// corrupt damages dst between the copy and the verifier, from the host, with
-// hipMemcpy inside the allocation and no kernel:
+// corrupt damages dst between the copy and the verifier (damage_from_host):
 //   ("flip", index, component, bit)   flips one bit of one float
 //   ("alias", index, distance)        element index := element index + distance
 py::dict hbm_copy_check(int device, long long n, long long blocks, int threads,
@@ -344,28 +375,14 @@ py::dict hbm_copy_check(int device, long long n, long long blocks, int threads,
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipDeviceSynchronize());
 
-    if (kind == kFlip) {
-        uint32_t *word = reinterpret_cast<uint32_t *>(out + c_index) + c_component;
-        uint32_t w = 0;
-        HIP_CHECK(hipMemcpy(&w, word, sizeof(w), hipMemcpyDeviceToHost));
-        w ^= 1u << c_bit;
-        HIP_CHECK(hipMemcpy(word, &w, sizeof(w), hipMemcpyHostToDevice));
-    } else if (kind == kAlias) {
-        HIP_CHECK(hipMemcpy(out + c_index, out + c_index + c_distance,
-                            sizeof(float4), hipMemcpyDeviceToDevice));
-    }
+    if (kind == kFlip)
+        damage_from_host(out + c_index, c_component, c_bit, nullptr);
+    else if (kind == kAlias)
+        damage_from_host(out + c_index, 0, 0, out + c_index + c_distance);
 
     const PatternResult verdict = verify_pattern(out, (size_t)n);
-
-    bool guard_ok = true;
-    std::vector<unsigned char> band((size_t)guard * sizeof(float4));
-    for (const float4 *from : {(const float4 *)dst.get(), (const float4 *)out + n}) {
-        if (band.empty()) break;
-        HIP_CHECK(hipMemcpy(band.data(), from, band.size(),
-                            hipMemcpyDeviceToHost));
-        for (unsigned char b : band)
-            if (b != hbmpattern::kPoisonByte) guard_ok = false;
-    }
+    const bool guard_ok = guards_hold_poison(
+        dst.get(), (size_t)guard * sizeof(float4), (size_t)n * sizeof(float4));
 
     const unsigned long long grid = (unsigned long long)blocks * threads;
     const unsigned long long un = (unsigned long long)n;
@@ -495,6 +512,16 @@ SimdId decode_hw_id(uint32_t hw_id, uint32_t xcc_id) {
             (int)(hw_id >> 8 & 15), (int)(hw_id >> 4 & 3)};
 }
 
+// where a result names a CU
+py::dict place_dict(int xcc, int se, int sh, int cu) {
+    py::dict d;
+    d["xcc"] = xcc;
+    d["se"] = se;
+    d["sh"] = sh;
+    d["cu"] = cu;
+    return d;
+}
+
 py::tuple decode_hw_id_py(uint32_t hw_id, uint32_t xcc_id) {
     SimdId id = decode_hw_id(hw_id, xcc_id);
     return py::make_tuple(id.xcc, id.se, id.sh, id.cu, id.simd);
@@ -505,6 +532,15 @@ int sweep_set_of(const std::string &name) {
     for (int s = 0; s < cusweepx::kSets; ++s)
         if (name == cusweepx::kSetName[s]) return s;
     throw std::invalid_argument("pipe_set must be base, mx or wide, not " + name);
+}
+
+// A runtime index i in 0..N-1 as a compile-time constant: the value of
+// fn(std::integral_constant<int, i>{}), there to choose a kernel instantiation.
+template <int N, typename Fn, int I = 0>
+auto with_index(int i, Fn &&fn) {
+    if constexpr (I + 1 < N)
+        if (i != I) return with_index<N, Fn, I + 1>(i, std::forward<Fn>(fn));
+    return fn(std::integral_constant<int, I>{});
 }
 
 // What one kind of sweep (CU sweep, VALU sweep) hands to the shared runner:
@@ -605,16 +641,11 @@ py::dict run_sweep(int device, int reps, const int inj[3], const SweepSpec &spec
         if (launches) reps = std::min(reps * 2, 1 << 16);
         ++launches;
         HIP_CHECK(hipMemset(d_rec.get(), 0, n_rec * sizeof(SweepRecord)));
-        HIP_CHECK(hipEventRecord(ev.start));
-        hipLaunchKernelGGL(spec.kernel, dim3(cu_count), dim3(256), lds_bytes, 0,
-                           d_table.get(), d_rec.get(), reps, inj[0], inj[1],
-                           inj[2]);
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipEventRecord(ev.stop));
-        HIP_CHECK(hipEventSynchronize(ev.stop));
-        float ms = 0;
-        HIP_CHECK(hipEventElapsedTime(&ms, ev.start, ev.stop));
-        sweep_ms += ms;
+        sweep_ms += ev.time([&] {
+            hipLaunchKernelGGL(spec.kernel, dim3(cu_count), dim3(256), lds_bytes,
+                               0, d_table.get(), d_rec.get(), reps, inj[0],
+                               inj[1], inj[2]);
+        });
         HIP_CHECK(hipMemcpy(h_rec.data(), d_rec.get(),
                             n_rec * sizeof(SweepRecord), hipMemcpyDeviceToHost));
 
@@ -642,11 +673,7 @@ py::dict run_sweep(int device, int reps, const int inj[3], const SweepSpec &spec
 
     py::list bad_list, uncovered;
     for (const auto &kv : bad) {
-        py::dict b;
-        b["xcc"] = kv.first.xcc;
-        b["se"] = kv.first.se;
-        b["sh"] = kv.first.sh;
-        b["cu"] = kv.first.cu;
+        py::dict b = place_dict(kv.first.xcc, kv.first.se, kv.first.sh, kv.first.cu);
         b["simd"] = kv.first.simd;
         b[spec.units_key] = sweep_unit_names(spec, kv.second.pipes);
         b["bad_lanes"] = kv.second.lanes;
@@ -655,11 +682,7 @@ py::dict run_sweep(int device, int reps, const int inj[3], const SweepSpec &spec
     }
     for (const auto &kv : simds_of_cu)
         if (kv.second != 0xF) {
-            py::dict u;
-            u["xcc"] = std::get<0>(kv.first);
-            u["se"] = std::get<1>(kv.first);
-            u["sh"] = std::get<2>(kv.first);
-            u["cu"] = std::get<3>(kv.first);
+            py::dict u = std::apply(place_dict, kv.first);
             py::list seen;
             for (int s = 0; s < 4; ++s)
                 if (kv.second >> s & 1) seen.append(s);
@@ -699,9 +722,9 @@ py::dict cu_sweep(int device, int reps, py::object inject,
     static std::vector<uint8_t> tables[cusweepx::kSets];
     if (tables[set].empty()) tables[set] = cusweepx::build_table(set);
     const SweepSpec spec = {
-        set == cusweepx::kBase ? cu_sweep_kernel<cusweepx::kBase>
-        : set == cusweepx::kMx ? cu_sweep_kernel<cusweepx::kMx>
-                               : cu_sweep_kernel<cusweepx::kWide>,
+        with_index<cusweepx::kSets>(set, [](auto s) -> SweepKernel {
+            return cu_sweep_kernel<decltype(s)::value>;
+        }),
         &tables[set], cusweepx::lds_bytes(set), cusweepx::n_pipes(set),
         [](int s, int p) { return cusweepx::pipe_name(s, p); }, set, "pipe", "pipes"};
     py::dict out = run_sweep(device, reps, inj, spec);
@@ -838,27 +861,6 @@ py::dict cu_sweep_reference(const std::string &pipe_set) {
 using RawKernel = void (*)(const unsigned char *, const unsigned char *,
                            const uint32_t *, const uint32_t *, uint32_t *);
 
-template <int SET, int P, int... I>
-RawKernel raw_kernel_of_sel(int sel, std::integer_sequence<int, I...>) {
-    static const RawKernel kernels[] = {mfma_raw_kernel<SET, P, I / 4, I % 4>...};
-    return kernels[sel];
-}
-
-template <int SET, int... P>
-RawKernel raw_kernel_of(int p, int sel, std::integer_sequence<int, P...>) {
-    RawKernel out = nullptr;
-    auto take = [&](auto pipe) {
-        constexpr int Q = decltype(pipe)::value;
-        if (p != Q) return;
-        if constexpr (SET == cusweepx::kMx)
-            out = raw_kernel_of_sel<SET, Q>(sel, std::make_integer_sequence<int, 16>{});
-        else
-            out = mfma_raw_kernel<SET, Q, 0, 0>;
-    };
-    (take(std::integral_constant<int, P>{}), ...);
-    return out;
-}
-
 // One product of one pipe of any set on one wave, from packed per-lane
 // fragments (and, for an mx pipe, the 64 scale words of each side and the
 // byte selects) laid out as in the tables: the raw result registers,
@@ -897,11 +899,20 @@ py::bytes mfma_raw(int device, const std::string &pipe, py::bytes a_frag,
         std::memcpy(&scales[(size_t)side * cusweepx::kLanes], raw.data(), raw.size());
     }
     const int code = sel.first * 4 + sel.second;
-    RawKernel kernel =
-        set == cusweepx::kBase
-            ? raw_kernel_of<cusweepx::kBase>(p, code, std::make_integer_sequence<int, cusweep::kPipes>{})
-        : mx ? raw_kernel_of<cusweepx::kMx>(p, code, std::make_integer_sequence<int, cusweepx::kMxPipes>{})
-             : raw_kernel_of<cusweepx::kWide>(p, code, std::make_integer_sequence<int, cusweepx::kWidePipes>{});
+    // an mx pipe's byte selects are template arguments
+    RawKernel kernel = with_index<cusweepx::kSets>(set, [&](auto s) {
+        constexpr int S = decltype(s)::value;
+        return with_index<cusweepx::n_pipes(S)>(p, [&](auto q) -> RawKernel {
+            constexpr int Q = decltype(q)::value;
+            if constexpr (S == cusweepx::kMx)
+                return with_index<16>(code, [](auto c) -> RawKernel {
+                    constexpr int C = decltype(c)::value;
+                    return mfma_raw_kernel<S, Q, C / 4, C % 4>;
+                });
+            else
+                return mfma_raw_kernel<S, Q, 0, 0>;
+        });
+    });
 
     HIP_CHECK(hipSetDevice(device));
     // every lane's operand load may read 32 bytes from its fragment's start
@@ -948,12 +959,6 @@ const std::vector<uint8_t> &valu_table(int set) {
     return tables[set];
 }
 
-template <int... S>
-SweepKernel valu_kernel_of(int set, std::integer_sequence<int, S...>) {
-    static const SweepKernel kernels[] = {valu_sweep_kernel<S>...};
-    return kernels[set];
-}
-
 // Known-answer vector, conversion, cross-lane, scalar and transcendental
 // ops on every SIMD of every CU (valu_sweep_kernel, run_sweep): the dict of
 // cu_sweep with `ops` and `op_set` in the place of `pipes` and `pipe_set`.
@@ -965,7 +970,9 @@ py::dict valu_sweep(int device, int reps, py::object inject,
     parse_sweep_inject(inject, valusweep::n_ops(set), "op", inj);
     reps = checked_sweep_reps(reps, kValuDefaultReps[set]);
     const SweepSpec spec = {
-        valu_kernel_of(set, std::make_integer_sequence<int, valusweep::kSets>{}),
+        with_index<valusweep::kSets>(set, [](auto s) -> SweepKernel {
+            return valu_sweep_kernel<decltype(s)::value>;
+        }),
         &valu_table(set), valusweep::lds_bytes(set), valusweep::n_ops(set),
         [](int s, int op) { return valusweep::desc(s, op).name; }, set, "op", "ops"};
     py::dict out = run_sweep(device, reps, inj, spec);
@@ -1011,25 +1018,6 @@ py::dict valu_sweep_reference(const std::string &op_set) {
 
 using ValuRawKernel = void (*)(const uint32_t *, uint32_t *);
 
-template <int SET, int... OP>
-ValuRawKernel valu_raw_kernel_of_op(int op, std::integer_sequence<int, OP...>) {
-    static const ValuRawKernel kernels[] = {valu_raw_kernel<SET, OP>...};
-    return kernels[op];
-}
-
-template <int... S>
-ValuRawKernel valu_raw_kernel_of(int set, int op, std::integer_sequence<int, S...>) {
-    ValuRawKernel out = nullptr;
-    auto take = [&](auto which) {
-        constexpr int Q = decltype(which)::value;
-        if (set == Q)
-            out = valu_raw_kernel_of_op<Q>(
-                op, std::make_integer_sequence<int, valusweep::n_ops(Q)>{});
-    };
-    (take(std::integral_constant<int, S>{}), ...);
-    return out;
-}
-
 // One wave of one op of any set on caller-supplied operand words: a, b, c
 // and old are 64 lanes x the descriptor's width of uint32 each, None where
 // the op takes none (the scalar ops and the lane selects read lane 0); the
@@ -1072,8 +1060,12 @@ py::bytes valu_raw(int device, const std::string &op_name, py::object a,
         for (int l = 0; l < valusweep::kLanes; ++l)
             std::memcpy(&in[(size_t)l * NI + at], raw.data() + (size_t)l * w * 4, (size_t)w * 4);
     }
-    ValuRawKernel kernel = valu_raw_kernel_of(
-        set, op, std::make_integer_sequence<int, valusweep::kSets>{});
+    ValuRawKernel kernel = with_index<valusweep::kSets>(set, [&](auto s) {
+        constexpr int S = decltype(s)::value;
+        return with_index<valusweep::n_ops(S)>(op, [](auto o) -> ValuRawKernel {
+            return valu_raw_kernel<S, decltype(o)::value>;
+        });
+    });
 
     HIP_CHECK(hipSetDevice(device));
     DeviceBuffer<uint32_t> d_in(in.size());
@@ -1104,6 +1096,28 @@ int march_pattern_by_name(const std::string &name) {
         if (name == hbmmarch::kPatternNames[p]) return p;
     throw std::invalid_argument("unknown pattern '" + name +
                                 "' (address, solid, checker, random)");
+}
+
+// A sequence of names of `what`s -> their indices by lookup (which throws on
+// an unknown name), in the order given: at least one, none twice.
+template <typename Lookup>
+std::vector<int> names_to_indices(const py::object &names, const std::string &what,
+                                  Lookup lookup) {
+    std::vector<int> out;
+    try {
+        for (py::handle h : names.cast<py::sequence>()) {
+            const int i = lookup(h.cast<std::string>());
+            if (std::find(out.begin(), out.end(), i) != out.end())
+                throw std::invalid_argument("a " + what + " is given twice");
+            out.push_back(i);
+        }
+    } catch (const py::cast_error &) {
+        throw std::invalid_argument(what + "s must be a sequence of names");
+    } catch (const py::type_error &) {
+        throw std::invalid_argument(what + "s must be a sequence of names");
+    }
+    if (out.empty()) throw std::invalid_argument(what + "s must name at least one");
+    return out;
 }
 
 const char *march_mode_name(int mode) {
@@ -1220,20 +1234,10 @@ py::dict hbm_scrub(int device, long long bytes, long long slab_bytes,
         throw std::invalid_argument("return_data needs bytes <= 16 * 2^21");
 
     std::vector<int> pats;
-    if (patterns.is_none()) {
+    if (patterns.is_none())
         for (int p = 0; p < hbmmarch::kPatterns; ++p) pats.push_back(p);
-    } else try {
-        for (py::handle h : patterns.cast<py::sequence>()) {
-            const int p = march_pattern_by_name(h.cast<std::string>());
-            if (std::find(pats.begin(), pats.end(), p) != pats.end())
-                throw std::invalid_argument("a pattern is given twice");
-            pats.push_back(p);
-        }
-        if (pats.empty())
-            throw std::invalid_argument("patterns must name at least one");
-    } catch (const py::cast_error &) {
-        throw std::invalid_argument("patterns must be a sequence of names");
-    }
+    else
+        pats = names_to_indices(patterns, "pattern", march_pattern_by_name);
 
     // one corruption, or a list of them
     std::vector<ScrubCorruption> damage;
@@ -1307,42 +1311,31 @@ py::dict hbm_scrub(int device, long long bytes, long long slab_bytes,
     EventPair ev;
     for (int p : pats) {
         for (int step = 0; step < hbmmarch::kSteps; ++step) {
-            HIP_CHECK(hipEventRecord(ev.start));
-            for (size_t k = 0; k < slabs.size(); ++k) {
-                // the descending step also takes the slabs from the top
-                const ScrubSlab &s =
-                    slabs[hbmmarch::step_descends(step) ? slabs.size() - 1 - k : k];
-                MarchParams a;
-                a.pattern = p;
-                a.step = step;
-                a.seed = seed;
-                a.base = s.base;
-                a.n = s.n;
-                a.max_records = (uint32_t)max_records;
-                launch_march(data_of(s), a, d_rep.get(), d_rec.get(),
-                             d_ranges.get());
-            }
-            HIP_CHECK(hipEventRecord(ev.stop));
-            HIP_CHECK(hipEventSynchronize(ev.stop));
-            float ms = 0;
-            HIP_CHECK(hipEventElapsedTime(&ms, ev.start, ev.stop));
+            const float ms = ev.time([&] {
+                for (size_t k = 0; k < slabs.size(); ++k) {
+                    // the descending step also takes the slabs from the top
+                    const ScrubSlab &s = slabs[hbmmarch::step_descends(step)
+                                                   ? slabs.size() - 1 - k : k];
+                    MarchParams a;
+                    a.pattern = p;
+                    a.step = step;
+                    a.seed = seed;
+                    a.base = s.base;
+                    a.n = s.n;
+                    a.max_records = (uint32_t)max_records;
+                    launch_march(data_of(s), a, d_rep.get(), d_rec.get(),
+                                 d_ranges.get());
+                }
+            });
             const int mode = march_mode_of_step(step);
             mode_ms[mode] += ms;
             mode_bytes[mode] += (mode == kMarchRW ? 2.0 : 1.0) * 16.0 * n_total;
 
             for (const ScrubCorruption &c : damage) {
                 if (c.pattern != p || c.after_step != step) continue;
-                if (c.kind == ScrubCorruption::kFlip) {
-                    char *word = address_of(c.element) + 4 * c.word;
-                    uint32_t w = 0;
-                    HIP_CHECK(hipMemcpy(&w, word, sizeof(w), hipMemcpyDeviceToHost));
-                    w ^= 1u << c.bit;
-                    HIP_CHECK(hipMemcpy(word, &w, sizeof(w), hipMemcpyHostToDevice));
-                } else {
-                    HIP_CHECK(hipMemcpy(address_of(c.element),
-                                        address_of(c.element + c.distance), 16,
-                                        hipMemcpyDeviceToDevice));
-                }
+                damage_from_host(address_of(c.element), c.word, c.bit,
+                                 c.kind == ScrubCorruption::kAlias
+                                     ? address_of(c.element + c.distance) : nullptr);
                 HIP_CHECK(hipDeviceSynchronize());
             }
         }
@@ -1359,17 +1352,8 @@ py::dict hbm_scrub(int device, long long bytes, long long slab_bytes,
                         n_ranges * sizeof(uint32_t), hipMemcpyDeviceToHost));
 
     bool guard_ok = true;
-    std::vector<unsigned char> band(guard_bytes);
-    for (const ScrubSlab &s : slabs) {
-        if (band.empty()) break;
-        for (const char *from : {(const char *)s.alloc,
-                                 (const char *)s.alloc + guard_bytes + s.n * 16}) {
-            HIP_CHECK(hipMemcpy(band.data(), from, band.size(),
-                                hipMemcpyDeviceToHost));
-            for (unsigned char b : band)
-                if (b != hbmpattern::kPoisonByte) guard_ok = false;
-        }
-    }
+    for (const ScrubSlab &s : slabs)
+        guard_ok &= guards_hold_poison(s.alloc, guard_bytes, s.n * 16);
     const double wall_ms =
         std::chrono::duration<double, std::milli>(
             std::chrono::steady_clock::now() - wall_start).count();
@@ -1560,37 +1544,15 @@ py::dict lds_sweep(int device, long long lds_bytes, long long blocks,
     if (reps == 0) reps = ldsmarch::kDefaultReps;
 
     bool path_on[ldsmarch::kPaths] = {};
-    if (paths.is_none()) {
+    if (paths.is_none())
         for (bool &on : path_on) on = true;
-    } else try {
-        bool any = false;
-        for (py::handle h : paths.cast<py::sequence>()) {
-            const int p = lds_path_by_name(h.cast<std::string>());
-            if (path_on[p]) throw std::invalid_argument("a path is given twice");
-            path_on[p] = any = true;
-        }
-        if (!any) throw std::invalid_argument("paths must name at least one");
-    } catch (const py::cast_error &) {
-        throw std::invalid_argument("paths must be a sequence of names");
-    } catch (const py::type_error &) {
-        throw std::invalid_argument("paths must be a sequence of names");
-    }
+    else
+        for (int p : names_to_indices(paths, "path", lds_path_by_name))
+            path_on[p] = true;
     uint32_t march_mask = 0;  // 0: each path's default
-    if (!patterns.is_none()) try {
-        for (py::handle h : patterns.cast<py::sequence>()) {
-            const uint32_t bit =
-                ldsmarch::pattern_bit(march_pattern_by_name(h.cast<std::string>()));
-            if (march_mask & bit)
-                throw std::invalid_argument("a pattern is given twice");
-            march_mask |= bit;
-        }
-        if (!march_mask)
-            throw std::invalid_argument("patterns must name at least one");
-    } catch (const py::cast_error &) {
-        throw std::invalid_argument("patterns must be a sequence of names");
-    } catch (const py::type_error &) {
-        throw std::invalid_argument("patterns must be a sequence of names");
-    }
+    if (!patterns.is_none())
+        for (int p : names_to_indices(patterns, "pattern", march_pattern_by_name))
+            march_mask |= ldsmarch::pattern_bit(p);
     uint32_t mask_of[ldsmarch::kPaths];
     for (int p = 0; p < ldsmarch::kPaths; ++p)
         mask_of[p] = !path_on[p] ? 0
@@ -1714,16 +1676,11 @@ py::dict lds_sweep(int device, long long lds_bytes, long long blocks,
         a.reps = (int)reps;
         HIP_CHECK(hipMemcpy(d_rec.get(), blanks.data(),
                             n_rec * sizeof(LdsBlockRecord), hipMemcpyHostToDevice));
-        HIP_CHECK(hipEventRecord(ev.start));
-        hipLaunchKernelGGL(lds_sweep_kernel, dim3((unsigned)blocks),
-                           dim3(ldsmarch::kThreads), (size_t)lds_bytes, 0, a,
-                           d_rec.get());
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipEventRecord(ev.stop));
-        HIP_CHECK(hipEventSynchronize(ev.stop));
-        float ms = 0;
-        HIP_CHECK(hipEventElapsedTime(&ms, ev.start, ev.stop));
-        sweep_ms += ms;
+        sweep_ms += ev.time([&] {
+            hipLaunchKernelGGL(lds_sweep_kernel, dim3((unsigned)blocks),
+                               dim3(ldsmarch::kThreads), (size_t)lds_bytes, 0, a,
+                               d_rec.get());
+        });
         HIP_CHECK(hipMemcpy(h_rec.data(), d_rec.get(),
                             n_rec * sizeof(LdsBlockRecord), hipMemcpyDeviceToHost));
 
@@ -1768,11 +1725,7 @@ py::dict lds_sweep(int device, long long lds_bytes, long long blocks,
         const hbmmarch::Element p = hbmmarch::pattern(
             (int)f.pattern, seed,
             ldsmarch::pattern_index((int)f.path, kv.second.block, elems, f.element));
-        py::dict b;
-        b["xcc"] = std::get<0>(kv.first);
-        b["se"] = std::get<1>(kv.first);
-        b["sh"] = std::get<2>(kv.first);
-        b["cu"] = std::get<3>(kv.first);
+        py::dict b = std::apply(place_dict, kv.first);
         b["mismatches"] = kv.second.mismatches;
         b["bad_bits"] = py::make_tuple(kv.second.bits[0], kv.second.bits[1],
                                        kv.second.bits[2], kv.second.bits[3]);

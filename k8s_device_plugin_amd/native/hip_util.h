@@ -1,6 +1,6 @@
 // Host-side HIP scaffolding shared by health_probe.hip and the sweeps:
-// a throwing HIP_CHECK, RAII device buffer and event pair, and the one
-// "warm up, record, run, record, sync, elapsed" timing helper.
+// a throwing HIP_CHECK, RAII device buffer and event pair with the one
+// "record, run, record, sync, elapsed" timing helper, and timed_ms on top.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -49,6 +49,20 @@ struct EventPair {
     }
     EventPair(const EventPair &) = delete;
     EventPair &operator=(const EventPair &) = delete;
+
+    // The milliseconds that launch() takes on the current device's null
+    // stream between the two events; a launch that failed throws.
+    template <typename Launch>
+    float time(Launch &&launch) {
+        HIP_CHECK(hipEventRecord(start));
+        launch();
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipEventRecord(stop));
+        HIP_CHECK(hipEventSynchronize(stop));
+        float ms = 0;
+        HIP_CHECK(hipEventElapsedTime(&ms, start, stop));
+        return ms;
+    }
 };
 
 // Runs warmup(), drains the device, then returns the milliseconds that
@@ -57,12 +71,5 @@ template <typename Warmup, typename Timed>
 float timed_ms(Warmup &&warmup, Timed &&timed) {
     warmup();
     HIP_CHECK(hipDeviceSynchronize());
-    EventPair ev;
-    HIP_CHECK(hipEventRecord(ev.start));
-    timed();
-    HIP_CHECK(hipEventRecord(ev.stop));
-    HIP_CHECK(hipEventSynchronize(ev.stop));
-    float ms = 0;
-    HIP_CHECK(hipEventElapsedTime(&ms, ev.start, ev.stop));
-    return ms;
+    return EventPair().time(timed);
 }

@@ -32,6 +32,19 @@ _COUNTER_HELP = {
     ),
 }
 
+# metric, help text, the plugin's {dev_id: count}
+_BAD_COUNT_GAUGES = (
+    ("amdgpu_dp_deep_probe_bad_simds",
+     "SIMDs that failed the last deep-probe CU sweep, summed over "
+     "GPUs (0 while the sweep is off)", "_sweep_bad_simds"),
+    ("amdgpu_dp_deep_probe_bad_lds_cus",
+     "CUs whose LDS failed the last deep-probe LDS sweep, summed over "
+     "GPUs (0 while the sweep is off)", "_sweep_bad_lds_cus"),
+    ("amdgpu_dp_deep_probe_bad_valu_simds",
+     "SIMDs that failed the last deep-probe VALU sweep, summed over "
+     "GPUs (0 while the sweep is off)", "_sweep_bad_valu_simds"),
+)
+
 
 class _ManagerCollector:
     """Prometheus collector reading live stats from the plugin manager."""
@@ -60,38 +73,12 @@ class _ManagerCollector:
             df.add_metric([resource], len(inst.plugin._deep_failed))
         yield df
 
-        bs = GaugeMetricFamily(
-            "amdgpu_dp_deep_probe_bad_simds",
-            "SIMDs that failed the last deep-probe CU sweep, summed over "
-            "GPUs (0 while the sweep is off)",
-            labels=["resource"],
-        )
-        for resource, inst in self.manager.plugins.items():
-            bs.add_metric([resource],
-                          sum(inst.plugin._sweep_bad_simds.values()))
-        yield bs
-
-        bl = GaugeMetricFamily(
-            "amdgpu_dp_deep_probe_bad_lds_cus",
-            "CUs whose LDS failed the last deep-probe LDS sweep, summed over "
-            "GPUs (0 while the sweep is off)",
-            labels=["resource"],
-        )
-        for resource, inst in self.manager.plugins.items():
-            bl.add_metric([resource],
-                          sum(inst.plugin._sweep_bad_lds_cus.values()))
-        yield bl
-
-        bv = GaugeMetricFamily(
-            "amdgpu_dp_deep_probe_bad_valu_simds",
-            "SIMDs that failed the last deep-probe VALU sweep, summed over "
-            "GPUs (0 while the sweep is off)",
-            labels=["resource"],
-        )
-        for resource, inst in self.manager.plugins.items():
-            bv.add_metric([resource],
-                          sum(inst.plugin._sweep_bad_valu_simds.values()))
-        yield bv
+        for name, help_text, attr in _BAD_COUNT_GAUGES:
+            bad = GaugeMetricFamily(name, help_text, labels=["resource"])
+            for resource, inst in self.manager.plugins.items():
+                bad.add_metric([resource],
+                               sum(getattr(inst.plugin, attr).values()))
+            yield bad
 
         counters = {}
         for resource, inst in self.manager.plugins.items():

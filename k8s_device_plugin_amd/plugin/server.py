@@ -82,24 +82,22 @@ class AMDGPUPlugin:
         self.deep_probe_every = deep_probe_every
         self._deep_beat = 0
         self._deep_failed: set = set()  # dev_ids that failed the deep probe
-        # with every deep probe (heartbeat and pre-start), also run the
-        # known-answer MFMA sweep of every CU and SIMD, on EVERY HIP ordinal
-        # of the physical GPU (in CPX mode each partition is an ordinal of
-        # its own, so all XCDs are covered)
+        # With every deep probe (heartbeat and pre-start), also run these
+        # sweeps of native.SWEEPS, on EVERY HIP ordinal of the physical GPU
+        # (in CPX mode each partition is an ordinal of its own, so all XCDs
+        # are covered); each flag is independent of the others.  CU sweep:
+        # known-answer MFMA on every CU and SIMD, and wherever it runs the
+        # extra pipe sets ("mx", "wide").  LDS sweep: march test of every CU's
+        # whole LDS.  VALU sweep: known-answer sweep of these op sets ("fma",
+        # "int", "cvt", "xlane", "salu", "trans").
         self.deep_cu_sweep = deep_cu_sweep
-        # the extra pipe sets ("mx", "wide") swept wherever the base sweep
-        # runs; _sweep_bad_simds counts distinct SIMDs over all sets
         self.deep_cu_sweep_extra = tuple(deep_cu_sweep_extra)
-        self._sweep_bad_simds: Dict[str, int] = {}  # dev_id -> last count
-        # likewise the march test of every CU's whole LDS (LDS sweep), on
-        # every ordinal; independent of the CU sweep
         self.deep_lds_sweep = deep_lds_sweep
-        self._sweep_bad_lds_cus: Dict[str, int] = {}  # dev_id -> last count
-        # likewise the known-answer sweep of these VALU op sets ("fma", "int",
-        # "cvt", "xlane", "salu", "trans"), on every ordinal; independent of
-        # the other sweeps.  _sweep_bad_valu_simds counts distinct SIMDs.
         self.deep_valu_sweep = tuple(deep_valu_sweep)
-        self._sweep_bad_valu_simds: Dict[str, int] = {}  # dev_id -> last count
+        # sweep key -> {dev_id: bad units of the last sweep}: SIMDs count
+        # once over all sets, LDS CUs are summed
+        self._sweep_bad: Dict[str, Dict[str, int]] = {
+            "cu_sweep": {}, "lds_sweep": {}, "valu_sweep": {}}
         self.dev_root = dev_root
         self.paths = paths
         self.devices: Dict[str, GPUDevice] = {}
@@ -113,6 +111,11 @@ class AMDGPUPlugin:
         self._heartbeat_gen = 0
         self._latest_list = None  # snapshot shared by all streams per beat
         self._stop = threading.Event()
+
+    # the per-sweep views of _sweep_bad that the metrics and the tests read
+    _sweep_bad_simds = property(lambda self: self._sweep_bad["cu_sweep"])
+    _sweep_bad_lds_cus = property(lambda self: self._sweep_bad["lds_sweep"])
+    _sweep_bad_valu_simds = property(lambda self: self._sweep_bad["valu_sweep"])
 
     # ---- lifecycle ----
 
@@ -219,20 +222,22 @@ class AMDGPUPlugin:
         """First HIP ordinal of the device's physical GPU."""
         return self._hip_ordinals(dev)[0]
 
+    def _deep_sweep_sets(self) -> Dict[str, tuple]:
+        """Sweep key -> the sets that the flags turn on (None: the sweep
+        itself, or the CU sweep's base set); empty = flag off."""
+        return {
+            "cu_sweep": ((None,) + self.deep_cu_sweep_extra
+                         if self.deep_cu_sweep else ()),
+            "lds_sweep": (None,) if self.deep_lds_sweep else (),
+            "valu_sweep": self.deep_valu_sweep,
+        }
+
     def _deep_probe(self, dev: GPUDevice) -> dict:
         """The deep probe of one physical GPU: MFMA/LDS/HBM with floors on
         its first HIP ordinal and, with deep_cu_sweep, deep_lds_sweep and /
         or deep_valu_sweep, that sweep on every ordinal, its bad-SIMD or
         bad-CU lines merged into floor_violations."""
-        from ..native import (
-            cu_sweep_violations,
-            deep_health_probe,
-            lds_sweep_with_ecc,
-            run_cu_sweep,
-            run_valu_sweep,
-            valu_sweep_incomplete_warning,
-            valu_sweep_violations,
-        )
+        from ..native import SWEEPS, check_sweep, deep_health_probe
 
         # hbm_scrub_bytes=0: never the HBM scrub here, whatever
         # AMDXDP_HBM_SCRUB_BYTES says; on a live node the pods own the VRAM.
@@ -240,83 +245,36 @@ class AMDGPUPlugin:
         # is off in the probe itself; one whose flag is off is left to the
         # environment, as before there were flags.
         ordinals = self._hip_ordinals(dev)
-        sweeps = {}
-        if self.deep_cu_sweep:
-            sweeps["cu_sweep"] = False
-        if self.deep_lds_sweep:
-            sweeps["lds_sweep"] = False
-        if self.deep_valu_sweep:
-            sweeps["valu_sweep"] = False
-        res = deep_health_probe(device=ordinals[0], hbm_scrub_bytes=0, **sweeps)
-        if self.deep_cu_sweep:
-            res["cu_sweep"] = {}
-            if self.deep_cu_sweep_extra:
-                res["cu_sweep_extra"] = {s: {} for s in self.deep_cu_sweep_extra}
-            bad_simds = set()  # a SIMD that fails in two sets counts once
+        flagged = {key: sets for key, sets in self._deep_sweep_sets().items()
+                   if sets}
+        res = deep_health_probe(device=ordinals[0], hbm_scrub_bytes=0,
+                                **dict.fromkeys(flagged, False))
+        for sweep in SWEEPS:
+            if sweep.key not in flagged:
+                continue
+            bad, unhealthy = [], False
             for ordinal in ordinals:
-                for pipe_set in ("base",) + self.deep_cu_sweep_extra:
-                    if pipe_set == "base":
-                        sweep = run_cu_sweep(ordinal)
-                        res["cu_sweep"][ordinal] = sweep
-                    else:
-                        sweep = run_cu_sweep(ordinal, pipe_set=pipe_set)
-                        res["cu_sweep_extra"][pipe_set][ordinal] = sweep
-                    for b in sweep.get("bad", []):
-                        bad_simds.add((ordinal, b["xcc"], b["se"], b["sh"],
-                                       b["cu"], b["simd"]))
-                    for line in cu_sweep_violations(sweep):
+                for which in flagged[sweep.key]:
+                    result, lines, warns = check_sweep(sweep, ordinal, which)
+                    sweep.place(res, which, result, ordinal)
+                    bad += [(ordinal, b["xcc"], b["se"], b["sh"], b["cu"],
+                             b.get("simd")) for b in result.get("bad", [])]
+                    for line in lines:
                         line = f"{line} (hip device {ordinal})"
                         log.error("deep probe on %s: %s", dev.dev_id, line)
                         res["floor_violations"].append(line)
-                    if sweep.get("ok") and not sweep.get("coverage_complete"):
-                        log.warning(
-                            "deep probe on %s: cu_sweep (%s pipes) reached %s "
-                            "of %s CUs on hip device %d", dev.dev_id, pipe_set,
-                            sweep.get("cus_covered"), sweep.get("cu_count"),
-                            ordinal,
-                        )
-            self._sweep_bad_simds[dev.dev_id] = len(bad_simds)
-            if bad_simds:
-                res["healthy"] = False
-        if self.deep_lds_sweep:
-            res["lds_sweep"] = {}
-            bad_cus = 0
-            unhealthy = False
-            for ordinal in ordinals:
-                sweep = lds_sweep_with_ecc(ordinal)
-                res["lds_sweep"][ordinal] = sweep
-                bad_cus += len(sweep.get("bad", []))
-                for line in sweep["violations"]:
-                    line = f"{line} (hip device {ordinal})"
-                    log.error("deep probe on %s: %s", dev.dev_id, line)
-                    res["floor_violations"].append(line)
-                    unhealthy = True
-                for line in sweep["warnings"]:
-                    log.warning("deep probe on %s: %s (hip device %d)",
-                                dev.dev_id, line, ordinal)
-            self._sweep_bad_lds_cus[dev.dev_id] = bad_cus
+                        unhealthy = True
+                    incomplete = sweep.incomplete(result, which)
+                    for line in warns:
+                        if sweep.plugin_incomplete and line == incomplete:
+                            line = sweep.plugin_incomplete(result, which, ordinal)
+                        else:
+                            line = f"{line} (hip device {ordinal})"
+                        log.warning("deep probe on %s: %s", dev.dev_id, line)
+            # a SIMD that fails in two sets counts once
+            self._sweep_bad[sweep.key][dev.dev_id] = (
+                len(set(bad)) if sweep.counts == "simds" else len(bad))
             if unhealthy:
-                res["healthy"] = False
-        if self.deep_valu_sweep:
-            res["valu_sweep"] = {s: {} for s in self.deep_valu_sweep}
-            bad_simds = set()  # a SIMD that fails in two sets counts once
-            for ordinal in ordinals:
-                for op_set in self.deep_valu_sweep:
-                    sweep = run_valu_sweep(ordinal, op_set=op_set)
-                    res["valu_sweep"][op_set][ordinal] = sweep
-                    for b in sweep.get("bad", []):
-                        bad_simds.add((ordinal, b["xcc"], b["se"], b["sh"],
-                                       b["cu"], b["simd"]))
-                    for line in valu_sweep_violations(sweep, op_set):
-                        line = f"{line} (hip device {ordinal})"
-                        log.error("deep probe on %s: %s", dev.dev_id, line)
-                        res["floor_violations"].append(line)
-                    warning = valu_sweep_incomplete_warning(sweep, op_set)
-                    if warning:
-                        log.warning("deep probe on %s: %s (hip device %d)",
-                                    dev.dev_id, warning, ordinal)
-            self._sweep_bad_valu_simds[dev.dev_id] = len(bad_simds)
-            if bad_simds:
                 res["healthy"] = False
         return res
 

@@ -7,7 +7,6 @@ The sweep itself runs on the GPU: tests/test_cu_sweep_gpu.py.
 import os
 import shutil
 import subprocess
-import types
 
 import numpy as np
 import pytest
@@ -17,6 +16,10 @@ from k8s_device_plugin_amd.native import build as nb
 from k8s_device_plugin_amd.plugin import AMDGPUPlugin
 from k8s_device_plugin_amd.protos import deviceplugin as dp
 from k8s_device_plugin_amd.testing.fakesysfs import build_mi355x_node
+
+from deep_probe_stubs import Ctx as _Ctx
+from deep_probe_stubs import ProbeOnlyStub as _ProbeOnlyStub
+from deep_probe_stubs import cpx_plugin, gauge, stub_probe  # noqa: F401
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NATIVE_DIR = os.path.join(REPO, "k8s_device_plugin_amd", "native")
@@ -217,19 +220,6 @@ _BAD_SIMD = {
 }
 
 
-class _ProbeOnlyStub:
-    """The module as it was before the sweep: run_probe and nothing else."""
-
-    def __init__(self):
-        self.calls = []
-
-    def run_probe(self, device=0, hbm_bytes=0):
-        self.calls.append(device)
-        return {"wave_ok": True, "mfma_ok": True, "lds_ok": True,
-                "hbm_copy_ok": True, "mfma_tflops": 2000.0,
-                "hbm_gbps": 6200.0, "healthy": True}
-
-
 class _SweepStub(_ProbeOnlyStub):
     def __init__(self, results=None, bus_ids=()):
         super().__init__()
@@ -243,18 +233,6 @@ class _SweepStub(_ProbeOnlyStub):
 
     def pci_bus_ids(self):
         return self.bus_ids
-
-
-@pytest.fixture
-def stub_probe(monkeypatch):
-    monkeypatch.delenv(native.CU_SWEEP_ENV, raising=False)
-    monkeypatch.delenv(native.CU_SWEEP_INJECT_ENV, raising=False)
-
-    def _install(mod):
-        monkeypatch.setattr(native, "load_healthprobe",
-                            lambda required=None: mod)
-        return mod
-    return _install
 
 
 def test_sweep_off_never_touches_cu_sweep(stub_probe):
@@ -322,33 +300,12 @@ def test_sweep_inject_env_is_parsed_and_passed(stub_probe, monkeypatch):
 # ---------------- plugin, metrics, CLI ----------------
 
 
-class _Ctx:
-    def is_active(self):
-        return True
-
-
-def _dev_root(tmp_path):
-    d = tmp_path / "dev"
-    d.mkdir(exist_ok=True)
-    (d / "kfd").touch()
-    return str(d)
-
-
 def _cpx_plugin(tmp_path, stub_probe, bad_ordinal=None, **kwargs):
-    """2 physical GPUs x 4 partitions; HIP ordinals 0-3 are GPU 0's
-    partitions and 4-7 GPU 1's (the same PCI bus id four times each)."""
-    fs = build_mi355x_node(str(tmp_path / "n"), n_gpus=2, partitions_per_gpu=4)
-    plugin = AMDGPUPlugin(resource="gpu", paths=fs.paths,
-                          dev_root=_dev_root(tmp_path), **kwargs)
-    plugin.start()
-    phys = sorted({d.dev_id for d in plugin.devices.values()})
-    assert len(phys) == 2
     results = {}
     if bad_ordinal is not None:
         results[bad_ordinal] = _sweep_result(bad=[_BAD_SIMD], cu_count=32)
-    mod = stub_probe(_SweepStub(
-        results, bus_ids=[phys[0]] * 4 + [phys[1]] * 4))
-    return plugin, mod, phys
+    return cpx_plugin(tmp_path, stub_probe,
+                      lambda bus_ids: _SweepStub(results, bus_ids), **kwargs)
 
 
 def test_plugin_sweeps_every_ordinal_of_the_gpu(tmp_path, stub_probe):
@@ -387,13 +344,7 @@ def test_plugin_bad_simd_pins_that_gpu_only(tmp_path, stub_probe, caplog):
     assert "cu_sweep: xcc 3 se 1 cu 7 simd 2 failed fp8_16" in caplog.text
 
     # the gauge reports the bad SIMDs of the last sweep, per resource
-    from k8s_device_plugin_amd.plugin.metrics import _ManagerCollector
-
-    manager = types.SimpleNamespace(
-        plugins={"gpu": types.SimpleNamespace(plugin=plugin, native=False)})
-    families = {f.name: f for f in _ManagerCollector(manager).collect()}
-    gauge = families["amdgpu_dp_deep_probe_bad_simds"]
-    assert [(s.labels, s.value) for s in gauge.samples] == [
+    assert gauge(plugin, "amdgpu_dp_deep_probe_bad_simds") == [
         ({"resource": "gpu"}, 1.0)]
 
     # recovery: the next sweep is clean -> unpinned, gauge back to 0
@@ -436,15 +387,10 @@ def test_prestart_deep_aborts_on_a_bad_simd(tmp_path, stub_probe):
 
 
 def test_gauge_is_zero_while_the_sweep_is_off(tmp_path, stub_probe):
-    from k8s_device_plugin_amd.plugin.metrics import _ManagerCollector
-
     plugin, _, _ = _cpx_plugin(tmp_path, stub_probe, deep_probe_every=1)
     plugin.heartbeat()
-    manager = types.SimpleNamespace(
-        plugins={"gpu": types.SimpleNamespace(plugin=plugin, native=False)})
-    families = {f.name: f for f in _ManagerCollector(manager).collect()}
-    assert [s.value for s in
-            families["amdgpu_dp_deep_probe_bad_simds"].samples] == [0.0]
+    assert [v for _, v in
+            gauge(plugin, "amdgpu_dp_deep_probe_bad_simds")] == [0.0]
     plugin.stop()
 
 

@@ -10,7 +10,6 @@ import os
 import shutil
 import struct
 import subprocess
-import types
 from fractions import Fraction
 
 import pytest
@@ -20,6 +19,10 @@ from k8s_device_plugin_amd.native import build as nb
 from k8s_device_plugin_amd.plugin import AMDGPUPlugin
 from k8s_device_plugin_amd.protos import deviceplugin as dp
 from k8s_device_plugin_amd.testing.fakesysfs import build_mi355x_node
+
+from deep_probe_stubs import Ctx as _Ctx
+from deep_probe_stubs import dev_root as _dev_root
+from deep_probe_stubs import cpx_plugin, gauge, stub_probe  # noqa: F401
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NATIVE_DIR = os.path.join(REPO, "k8s_device_plugin_amd", "native")
@@ -478,19 +481,6 @@ class _ExtStub(_BaseOnlyStub):
         return self.results.get((device, pipe_set)) or _sweep_result(pipe_set)
 
 
-@pytest.fixture
-def stub_probe(monkeypatch):
-    for env in (native.CU_SWEEP_ENV, native.CU_SWEEP_INJECT_ENV,
-                native.CU_SWEEP_EXTRA_ENV):
-        monkeypatch.delenv(env, raising=False)
-
-    def _install(mod):
-        monkeypatch.setattr(native, "load_healthprobe",
-                            lambda required=None: mod)
-        return mod
-    return _install
-
-
 def test_extra_sets_are_off_by_default(stub_probe):
     mod = stub_probe(_BaseOnlyStub())  # would raise on a pipe_set keyword
     res = native.deep_health_probe(device=2, cu_sweep=True)
@@ -596,38 +586,13 @@ def test_inject_env_errors(stub_probe, monkeypatch, spec):
 # ---------------- plugin, metrics, CLI ----------------
 
 
-class _Ctx:
-    def is_active(self):
-        return True
-
-
-def _dev_root(tmp_path):
-    d = tmp_path / "dev"
-    d.mkdir(exist_ok=True)
-    (d / "kfd").touch()
-    return str(d)
-
-
 def _cpx_plugin(tmp_path, stub_probe, results=None, **kwargs):
-    """2 physical GPUs x 4 partitions; HIP ordinals 0-3 are GPU 0's
-    partitions and 4-7 GPU 1's."""
-    fs = build_mi355x_node(str(tmp_path / "n"), n_gpus=2, partitions_per_gpu=4)
-    plugin = AMDGPUPlugin(resource="gpu", paths=fs.paths,
-                          dev_root=_dev_root(tmp_path), **kwargs)
-    plugin.start()
-    phys = sorted({d.dev_id for d in plugin.devices.values()})
-    assert len(phys) == 2
-    mod = stub_probe(_ExtStub(results, bus_ids=[phys[0]] * 4 + [phys[1]] * 4))
-    return plugin, mod, phys
+    return cpx_plugin(tmp_path, stub_probe,
+                      lambda bus_ids: _ExtStub(results, bus_ids), **kwargs)
 
 
 def _gauge(plugin):
-    from k8s_device_plugin_amd.plugin.metrics import _ManagerCollector
-
-    manager = types.SimpleNamespace(
-        plugins={"gpu": types.SimpleNamespace(plugin=plugin, native=False)})
-    families = {f.name: f for f in _ManagerCollector(manager).collect()}
-    return [s.value for s in families["amdgpu_dp_deep_probe_bad_simds"].samples]
+    return [v for _, v in gauge(plugin, "amdgpu_dp_deep_probe_bad_simds")]
 
 
 def test_plugin_runs_the_extra_sets_on_every_ordinal(tmp_path, stub_probe):

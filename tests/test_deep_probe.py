@@ -15,6 +15,10 @@ from k8s_device_plugin_amd.plugin import AMDGPUPlugin
 from k8s_device_plugin_amd.protos import deviceplugin as dp
 from k8s_device_plugin_amd.testing.fakesysfs import build_mi355x_node
 
+from deep_probe_stubs import Ctx as _Ctx
+from deep_probe_stubs import dev_root as _dev_root
+from deep_probe_stubs import stub_probe  # noqa: F401
+
 
 class _StubProbeMod:
     def __init__(self, mfma=2000.0, hbm=6200.0, ok=True):
@@ -32,15 +36,6 @@ class _StubProbeMod:
             "hbm_gbps": self.hbm,
             "healthy": self.ok,
         }
-
-
-@pytest.fixture
-def stub_probe(monkeypatch):
-    def _install(mod):
-        monkeypatch.setattr(native, "load_healthprobe",
-                            lambda required=None: mod)
-        return mod
-    return _install
 
 
 def test_floor_pass(stub_probe):
@@ -81,19 +76,6 @@ def test_explicit_floor_args(stub_probe):
     assert res["healthy"]
     res = native.deep_health_probe(mfma_floor_tflops=1100, hbm_floor_gbps=4000)
     assert not res["healthy"]
-
-
-class _Ctx:
-    def is_active(self):
-        return True
-
-
-def _dev_root(tmp_path):
-    d = tmp_path / "dev"
-    d.mkdir(exist_ok=True)
-    (d / "kfd").touch()
-    return str(d)
-
 
 
 def test_heartbeat_deep_check_flips_unhealthy(tmp_path, stub_probe):

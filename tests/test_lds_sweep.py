@@ -8,7 +8,6 @@ The sweep itself runs on the GPU: tests/test_lds_sweep_gpu.py.
 import os
 import shutil
 import subprocess
-import types
 
 import numpy as np
 import pytest
@@ -18,6 +17,10 @@ from k8s_device_plugin_amd.native import build as nb
 from k8s_device_plugin_amd.plugin import AMDGPUPlugin
 from k8s_device_plugin_amd.protos import deviceplugin as dp
 from k8s_device_plugin_amd.testing.fakesysfs import build_mi355x_node
+
+from deep_probe_stubs import Ctx as _Ctx
+from deep_probe_stubs import ProbeOnlyStub as _ProbeOnlyStub
+from deep_probe_stubs import cpx_plugin, gauge, stub_probe  # noqa: F401
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NATIVE_DIR = os.path.join(REPO, "k8s_device_plugin_amd", "native")
@@ -225,19 +228,6 @@ _BAD_LINE = ("lds_sweep: xcc 3 se 1 cu 7: 2 bad accesses (path b128 pattern "
 BDF = "0000:05:00.0"
 
 
-class _ProbeOnlyStub:
-    """The module as it was before the sweep: run_probe and nothing else."""
-
-    def __init__(self):
-        self.calls = []
-
-    def run_probe(self, device=0, hbm_bytes=0):
-        self.calls.append(device)
-        return {"wave_ok": True, "mfma_ok": True, "lds_ok": True,
-                "hbm_copy_ok": True, "mfma_tflops": 2000.0,
-                "hbm_gbps": 6200.0, "healthy": True}
-
-
 class _CuSweepStub(_ProbeOnlyStub):
     """The module as it was at the parent commit: no lds_sweep."""
 
@@ -271,20 +261,6 @@ class _LdsStub(_CuSweepStub):
         if self.during:
             self.during()
         return dict(self.results.get(device) or _lds_result())
-
-
-@pytest.fixture
-def stub_probe(monkeypatch):
-    for env in (native.CU_SWEEP_ENV, native.CU_SWEEP_INJECT_ENV,
-                native.LDS_SWEEP_ENV, native.LDS_SWEEP_INJECT_ENV,
-                native.HBM_SCRUB_ENV):
-        monkeypatch.delenv(env, raising=False)
-
-    def _install(mod):
-        monkeypatch.setattr(native, "load_healthprobe",
-                            lambda required=None: mod)
-        return mod
-    return _install
 
 
 def test_off_is_key_for_key_as_before(stub_probe):
@@ -440,41 +416,12 @@ def test_read_ecc_counts_default_is_umc(tmp_path):
 # ---------------- plugin, metrics, CLI ----------------
 
 
-class _Ctx:
-    def is_active(self):
-        return True
-
-
-def _dev_root(tmp_path):
-    d = tmp_path / "dev"
-    d.mkdir(exist_ok=True)
-    (d / "kfd").touch()
-    return str(d)
-
-
 def _cpx_plugin(tmp_path, stub_probe, bad_ordinal=None, **kwargs):
-    """2 physical GPUs x 4 partitions; HIP ordinals 0-3 are GPU 0's
-    partitions and 4-7 GPU 1's (the same PCI bus id four times each)."""
-    fs = build_mi355x_node(str(tmp_path / "n"), n_gpus=2, partitions_per_gpu=4)
-    plugin = AMDGPUPlugin(resource="gpu", paths=fs.paths,
-                          dev_root=_dev_root(tmp_path), **kwargs)
-    plugin.start()
-    phys = sorted({d.dev_id for d in plugin.devices.values()})
-    assert len(phys) == 2
     results = {}
     if bad_ordinal is not None:
         results[bad_ordinal] = _lds_result(bad=[_BAD_CU], cu_count=32)
-    mod = stub_probe(_LdsStub(
-        results, bus_ids=[phys[0]] * 4 + [phys[1]] * 4))
-    return plugin, mod, phys
-
-
-def _gauges(plugin):
-    from k8s_device_plugin_amd.plugin.metrics import _ManagerCollector
-
-    manager = types.SimpleNamespace(
-        plugins={"gpu": types.SimpleNamespace(plugin=plugin, native=False)})
-    return {f.name: f for f in _ManagerCollector(manager).collect()}
+    return cpx_plugin(tmp_path, stub_probe,
+                      lambda bus_ids: _LdsStub(results, bus_ids=bus_ids), **kwargs)
 
 
 def test_plugin_sweeps_every_ordinal_of_the_gpu(tmp_path, stub_probe):
@@ -496,8 +443,8 @@ def test_plugin_without_the_flag_does_not_sweep(tmp_path, stub_probe):
     plugin.heartbeat()
     assert mod.calls == [0, 4] and mod.sweeps == [] and mod.cu_sweeps == []
     assert plugin._sweep_bad_lds_cus == {}
-    assert [s.value for s in
-            _gauges(plugin)["amdgpu_dp_deep_probe_bad_lds_cus"].samples] == [0.0]
+    assert [v for _, v in
+            gauge(plugin, "amdgpu_dp_deep_probe_bad_lds_cus")] == [0.0]
     plugin.stop()
 
 
@@ -518,11 +465,10 @@ def test_plugin_bad_cu_pins_that_gpu_only_and_recovers(tmp_path, stub_probe,
     assert _BAD_LINE + " (hip device 6)" in caplog.text
 
     # the gauge reports the bad CUs of the last sweep, per resource
-    gauge = _gauges(plugin)["amdgpu_dp_deep_probe_bad_lds_cus"]
-    assert [(s.labels, s.value) for s in gauge.samples] == [
+    assert gauge(plugin, "amdgpu_dp_deep_probe_bad_lds_cus") == [
         ({"resource": "gpu"}, 1.0)]
-    assert [s.value for s in
-            _gauges(plugin)["amdgpu_dp_deep_probe_bad_simds"].samples] == [0.0]
+    assert [v for _, v in
+            gauge(plugin, "amdgpu_dp_deep_probe_bad_simds")] == [0.0]
 
     # recovery: the next sweep is clean -> unpinned, gauge back to 0
     mod.results.clear()

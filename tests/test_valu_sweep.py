@@ -13,7 +13,6 @@ import re
 import shutil
 import struct
 import subprocess
-import types
 
 import pytest
 
@@ -24,6 +23,8 @@ from k8s_device_plugin_amd.plugin import AMDGPUPlugin
 from k8s_device_plugin_amd.protos import deviceplugin as dp
 from k8s_device_plugin_amd.testing.fakesysfs import build_mi355x_node
 
+from deep_probe_stubs import Ctx as _Ctx
+from deep_probe_stubs import cpx_plugin, gauge, stub_probe  # noqa: F401
 from valu_reference import REFERENCE
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -288,19 +289,6 @@ class _ValuStub:
         return dict(res or _sweep_result())
 
 
-@pytest.fixture
-def stub_probe(monkeypatch):
-    for env in (native.CU_SWEEP_ENV, native.CU_SWEEP_INJECT_ENV,
-                native.LDS_SWEEP_ENV, native.HBM_SCRUB_ENV,
-                native.VALU_SWEEP_ENV, native.VALU_SWEEP_INJECT_ENV):
-        monkeypatch.delenv(env, raising=False)
-
-    def _install(mod):
-        monkeypatch.setattr(native, "load_healthprobe", lambda required=None: mod)
-        return mod
-    return _install
-
-
 def test_off_by_default(stub_probe):
     mod = stub_probe(_ValuStub())
     res = native.deep_health_probe()
@@ -418,41 +406,16 @@ def test_inject_errors(stub_probe, monkeypatch, spec):
 # ---------------- plugin, metrics, CLI ----------------
 
 
-class _Ctx:
-    def is_active(self):
-        return True
-
-
-def _dev_root(tmp_path):
-    d = tmp_path / "dev"
-    d.mkdir(exist_ok=True)
-    (d / "kfd").touch()
-    return str(d)
-
-
 def _cpx_plugin(tmp_path, stub_probe, bad=None, **kwargs):
-    """2 physical GPUs x 4 partitions; HIP ordinals 0-3 are GPU 0's
-    partitions and 4-7 GPU 1's (the same PCI bus id four times each)."""
-    fs = build_mi355x_node(str(tmp_path / "n"), n_gpus=2, partitions_per_gpu=4)
-    plugin = AMDGPUPlugin(resource="gpu", paths=fs.paths,
-                          dev_root=_dev_root(tmp_path), **kwargs)
-    plugin.start()
-    phys = sorted({d.dev_id for d in plugin.devices.values()})
-    assert len(phys) == 2
     results = {}
     if bad is not None:
         results[bad] = _sweep_result(bad=[_BAD_SIMD], cu_count=32)
-    mod = stub_probe(_ValuStub(results, bus_ids=[phys[0]] * 4 + [phys[1]] * 4))
-    return plugin, mod, phys
+    return cpx_plugin(tmp_path, stub_probe,
+                      lambda bus_ids: _ValuStub(results, bus_ids=bus_ids), **kwargs)
 
 
 def _gauge(plugin, name="amdgpu_dp_deep_probe_bad_valu_simds"):
-    from k8s_device_plugin_amd.plugin.metrics import _ManagerCollector
-
-    manager = types.SimpleNamespace(
-        plugins={"gpu": types.SimpleNamespace(plugin=plugin, native=False)})
-    families = {f.name: f for f in _ManagerCollector(manager).collect()}
-    return [(s.labels, s.value) for s in families[name].samples]
+    return gauge(plugin, name)
 
 
 def test_plugin_sweeps_every_ordinal_of_the_gpu(tmp_path, stub_probe):
